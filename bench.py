@@ -11,6 +11,11 @@ C4-sized month range of an N x 10,000-day panel.
 A step = one full pass over the resident panel: month-end aggregation, [summary all-gather +
 carry fold when N>1], ret/mom/next_ret scan, per-date qcut labels fused with decile means,
 [per-date row all-gather when N>1], long-short.  Inputs are in HBM before timing starts.
+
+A plain run sets up, warms up, times --steps steps and prints the JSON line (--dump-outputs DIR
+also writes the last timed step's outputs).  --full adds what takes runs of its own: the CPU
+baseline, the decile-match check against the oracle, and the per-stage times and rooflines that
+need an untimed pass.
 """
 from __future__ import annotations
 
@@ -72,7 +77,17 @@ def parse(argv=None):
                          "daily rows; only the assets the halo leaves uncertain are exchanged), "
                          "speculative fused signal + all-gather + repair, or month-end + carried "
                          "scan")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure, each in a run of its own after the "
+                         "timed steps: the CPU baseline, the decile-match check against the oracle, "
+                         "and the per-stage times and rooflines that need an untimed pass (C2's "
+                         "hipGraph, the sweeps)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step computed as DIR/<name>.npy "
+                         "(finite float64, with <name>_nonfinite.npy marking the NaN cells; wide "
+                         "arrays as a fixed seeded sample of their columns, 64 MB in all at the most)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full: skip the CPU baseline")
     ap.add_argument("--cpu-assets", type=int, default=150000)   # ~10-15 s of oracle time
     ap.add_argument("--seed", type=int, default=4)
     ap.add_argument("--no-ids", action="store_true",
@@ -88,10 +103,10 @@ def parse(argv=None):
                     help="C2 A/B: k_month_end + the three-launch chunked scan (summary, fold, scan) "
                          "instead of the one-launch month-end + chunked scan (csm_signal_chunked)")
     ap.add_argument("--no-oracle-mom", action="store_true",
-                    help="N = 1 decile check: qcut the engine's mom_J instead of the oracle's own "
+                    help="--full, N = 1 decile check: qcut the engine's mom_J instead of the oracle's own "
                          "month-end + scan of the panel (that pass adds ~10-20 s at C4)")
     ap.add_argument("--match-dates", type=int, default=0,
-                    help="decile-match check on this many evenly spaced dates (0 = every date)")
+                    help="--full: decile-match check on this many evenly spaced dates (0 = every date)")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="replay the step as one captured hipGraph (auto: the unfused narrow "
                          "panels, C2, where launch gaps are a large share of the step; C3 on one "
@@ -137,6 +152,45 @@ def apply_tunes(eng, tunes):
         k, v = kv.split("=")
         if eng.lib.csm_tune(k.encode(), int(v)) != 0:
             raise SystemExit(f"csm_tune({k}, {v}) rejected")
+
+
+DUMP_BUDGET = 48 << 20     # bytes for the sampled wide arrays of --dump-outputs
+DUMP_SEED = 20240611
+
+
+def _save_finite(d, name, a):
+    """One array as finite float64 DIR/<name>.npy.  A floating-point array (its NaNs mean "no
+    value": months before the look-back, absent assets, empty deciles) is written with its
+    non-finite cells as 0 and DIR/<name>_nonfinite.npy (float32) saying which they were:
+    0 finite, 1 NaN, 2 +inf, 3 -inf."""
+    a = np.ascontiguousarray(a)
+    if np.issubdtype(a.dtype, np.floating):
+        code = np.where(np.isnan(a), 1, np.where(a == np.inf, 2, np.where(a == -np.inf, 3, 0)))
+        np.save(d / f"{name}_nonfinite.npy", code.astype(np.float32))
+        a = np.where(code == 0, a, 0.0)
+    np.save(d / f"{name}.npy", a.astype(np.float64))
+
+
+def dump_outputs(dirname, small, wide=None):
+    """--dump-outputs: every array of `small` whole and, of the (rows, N) device arrays in `wide`,
+    the same fixed seeded sample of columns (DIR/columns.npy lists them), as finite .npy files
+    (_save_finite)."""
+    d = Path(dirname)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in small.items():
+        _save_finite(d, name, a.cpu().numpy())
+    if not wide:
+        return
+    import torch
+    rows = max(int(a.shape[0]) for a in wide.values())
+    N = int(next(iter(wide.values())).shape[1])
+    cell = sum(12 if a.dtype.is_floating_point else 8 for a in wide.values())   # bytes written
+    k = int(min(N, max(1, DUMP_BUDGET // (cell * rows))))
+    cols = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=k, replace=False))
+    np.save(d / "columns.npy", cols.astype(np.float64))
+    for name, a in wide.items():
+        idx = torch.from_numpy(cols).to(a.device)
+        _save_finite(d, name, a.index_select(1, idx).cpu().numpy())
 
 
 def cpu_baseline(n_assets: int, days: int, start: str):
@@ -314,6 +368,56 @@ def committed_profile(config, N, T_d, lib_hash):
     return None
 
 
+def decile_match(args, Mh, Lh, panel, ms_host, J, skip, nb, world, dev, tm_all):
+    """--full: decile match vs the oracle (metric: "decile match %"): the oracle's qcut on the
+    engine's mom_J for every date (or --match-dates evenly spaced ones), labels compared cell by
+    cell.  N > 1: every rank checks its own months; the counts are summed over the ranks.
+    Returns (match, mom_bit_exact_pct)."""
+    import torch.distributed as dist
+    from oracle import csmom_oracle as O
+    T_m, N = Mh.shape
+    if args.match_dates > 0:
+        dates = sorted({int(x) for x in np.linspace(0, T_m - 1, args.match_dates)})
+    else:
+        dates = list(range(T_m))
+    # N = 1: the reference labels come from the ORACLE's mom_J -- the oracle's month-end and scan
+    # over this very panel, in column blocks (per-asset arithmetic: a block is exact) -- and the
+    # engine's mom_J is checked against it bit for bit on every cell
+    Mo, mom_exact = None, None
+    if world == 1 and not args.no_oracle_mom:
+        Mo = np.empty((T_m, N))
+        same = 0
+        for c0 in range(0, N, 20_000):
+            c1 = min(N, c0 + 20_000)
+            PMb, _ = O.month_end(panel.P[:, c0:c1].cpu().numpy(), ms_host)
+            _, Mb, _, _ = O.momentum_scan(PMb, J, skip)
+            Mo[:, c0:c1] = Mb
+            same += int((Mb.view(np.uint64) == Mh[:, c0:c1].cpu().numpy().view(np.uint64)).sum())
+        mom_exact = 100.0 * same / (T_m * N)
+    tot = ok = 0
+    for t0 in range(0, len(dates), 64):
+        blk = dates[t0:t0 + 64]
+        mrows = Mo[blk] if Mo is not None else Mh[blk].cpu().numpy()
+        lrows = Lh[blk].cpu().numpy()
+        for row, got in zip(mrows, lrows):
+            ref = np.full(N, -1, dtype=np.int8)
+            v = ~np.isnan(row)
+            if v.any():
+                lab = O.qcut_labels(row[v], nb)
+                ref[v] = np.where(np.isnan(lab), -1, lab).astype(np.int8)
+            ok += int((got == ref).sum())
+            tot += N
+    ok, tot, ndates = allreduce_host([ok, tot, len(dates)],
+                                     dist.ReduceOp.SUM if world > 1 else None, dev)
+    match = dict(pct=100.0 * ok / tot,
+                 sample=f"{int(ndates)} of {tm_all} dates x {N} assets"
+                        f"{f' (all {world} ranks)' if world > 1 else ''}: oracle qcut of the "
+                        + ("ORACLE's mom_J (oracle month-end + scan on this panel; engine mom_J "
+                           f"bit-exact on {mom_exact:.4f} % of cells)" if Mo is not None
+                           else "engine's mom_J"))
+    return match, mom_exact
+
+
 def main(argv=None):
     args = parse(argv)
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
@@ -406,11 +510,15 @@ def main(argv=None):
                    for _ in range(args.steps)]
     scratch_events = [torch.cuda.Event(enable_timing=True) for _ in range(nst)]
 
+    last = SimpleNamespace(res=None)   # N > 1: what the latest step returned (--dump-outputs)
+
     def step(ev=scratch_events):
         if pipe is not None:
             if halo:   # (the fallback list's fit is checked once, after the timed loop)
-                return pipe.run_halo(hp.P, hp.month_start, hp.H, hp.F, max_days, check=False).LS
-            r = pipe.run(panel.P, panel.month_start, max_days)
+                r = pipe.run_halo(hp.P, hp.month_start, hp.H, hp.F, max_days, check=False)
+            else:
+                r = pipe.run(panel.P, panel.month_start, max_days)
+            last.res = r
             return r.LS
         rec = (lambda e: e.record()) if ev is not None else (lambda e: None)
         ev = ev if ev is not None else [None] * nst
@@ -477,7 +585,7 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if graph is not None:   # per-stage device times from an untimed eager pass
+    if graph is not None and args.full:   # per-stage device times from an untimed eager pass
         for k in range(args.steps):
             step(step_events[k])
         torch.cuda.synchronize()
@@ -490,75 +598,43 @@ def main(argv=None):
         except Exception as e:
             raise SystemExit(f"C2 signal: {e}; the timed passes are invalid, no line printed")
 
-    if world == 1:
+    # per-stage times: the timed loop's own events (eager steps), or --full's eager pass (hipGraph)
+    have_stages = world == 1 and (graph is None or args.full)
+    if have_stages:
         for ev in step_events:
             stage_ms += [ev[i].elapsed_time(ev[i + 1]) for i in range(len(stage_names))]
     else:
         stage_ms[:] = np.nan
 
-    # decile match vs the oracle (metric: "decile match %"): the oracle's qcut on the engine's
-    # mom_J for every date (or --match-dates evenly spaced ones), labels compared cell by cell.
-    # N > 1: EVERY rank runs the (collective-bearing) pass and checks its own months; the
-    # counts are summed over the ranks.
-    from oracle import csmom_oracle as O
     halo_info = None
-    if world > 1:
-        if halo:   # the timed passes' list fit (every rank sees the same list); then a checked pass
-            cnt, cap = pipe.last_count
-            listed = int(cnt.max().item())
-            if listed > cap:
-                raise SystemExit(f"halo pass: {listed} listed assets exceed the list width {cap}; "
-                                 "the timed passes are invalid (rerun with --shard-mode fused)")
-            halo_info = dict(H=hp.H, F=hp.F, listed_assets=listed, list_width=cap,
-                             rows_read_with_halo=int(hp.P.shape[0]), shard_days=hp.shard_days)
-            res = pipe.run_halo(hp.P, hp.month_start, hp.H, hp.F, max_days)
-        else:
-            res = pipe.run(panel.P, panel.month_start, max_days)
-        Mh, Lh, LSh, EWh, CNTh = res.M, res.L, res.LS, res.EW, res.CNT
+    if halo:   # the timed passes' list fit (every rank sees the same list)
+        cnt, cap = pipe.last_count
+        listed = int(cnt.max().item())
+        if listed > cap:
+            raise SystemExit(f"halo pass: {listed} listed assets exceed the list width {cap}; "
+                             "the timed passes are invalid (rerun with --shard-mode fused)")
+        halo_info = dict(H=hp.H, F=hp.F, listed_assets=listed, list_width=cap,
+                         rows_read_with_halo=int(hp.P.shape[0]), shard_days=hp.shard_days)
+    if world == 1:
+        res = SimpleNamespace(M=M, NR=NR, L=L, LS=LS, EW=EW, CNT=CNT)
+    elif not args.full:
+        res = last.res        # the last timed step's
+    elif halo:                # --full, N > 1: EVERY rank runs a checked (collective-bearing) pass
+        res = pipe.run_halo(hp.P, hp.month_start, hp.H, hp.F, max_days)
     else:
-        Mh, Lh, LSh, EWh, CNTh = M, L, LS, EW, CNT
-    if args.match_dates > 0:
-        dates = sorted({int(x) for x in np.linspace(0, T_m - 1, args.match_dates)})
-    else:
-        dates = list(range(T_m))
-    # N = 1: the reference labels come from the ORACLE's mom_J -- the oracle's month-end and scan
-    # over this very panel, in column blocks (per-asset arithmetic: a block is exact) -- and the
-    # engine's mom_J is checked against it bit for bit on every cell
-    Mo, mom_exact = None, None
-    if world == 1 and not args.no_oracle_mom:
-        Mo = np.empty((T_m, N))
-        same = 0
-        for c0 in range(0, N, 20_000):
-            c1 = min(N, c0 + 20_000)
-            PMb, _ = O.month_end(panel.P[:, c0:c1].cpu().numpy(), ms_host)
-            _, Mb, _, _ = O.momentum_scan(PMb, J, skip)
-            Mo[:, c0:c1] = Mb
-            same += int((Mb.view(np.uint64) == Mh[:, c0:c1].cpu().numpy().view(np.uint64)).sum())
-        mom_exact = 100.0 * same / (T_m * N)
-    tot = ok = 0
-    for t0 in range(0, len(dates), 64):
-        blk = dates[t0:t0 + 64]
-        mrows = Mo[blk] if Mo is not None else Mh[blk].cpu().numpy()
-        lrows = Lh[blk].cpu().numpy()
-        for row, got in zip(mrows, lrows):
-            ref = np.full(N, -1, dtype=np.int8)
-            v = ~np.isnan(row)
-            if v.any():
-                lab = O.qcut_labels(row[v], nb)
-                ref[v] = np.where(np.isnan(lab), -1, lab).astype(np.int8)
-            ok += int((got == ref).sum())
-            tot += N
-    ok, tot, ndates = allreduce_host([ok, tot, len(dates)],
-                                     dist.ReduceOp.SUM if world > 1 else None, dev)
-    tm_all = sum(pipe.months) if pipe is not None else T_m
-    match = dict(pct=100.0 * ok / tot,
-                 sample=f"{int(ndates)} of {tm_all} dates x {N} assets"
-                        f"{f' (all {world} ranks)' if world > 1 else ''}: oracle qcut of the "
-                        + ("ORACLE's mom_J (oracle month-end + scan on this panel; engine mom_J "
-                           f"bit-exact on {mom_exact:.4f} % of cells)" if Mo is not None
-                           else "engine's mom_J"))
+        res = pipe.run(panel.P, panel.month_start, max_days)
+    if rank == 0 and args.dump_outputs:
+        if res is None:
+            raise SystemExit("--dump-outputs needs at least one step (--steps or --warmup > 0)")
+        wide = {k: getattr(res, k) for k in ("M", "NR", "L") if getattr(res, k, None) is not None}
+        dump_outputs(args.dump_outputs, dict(LS=res.LS, EW=res.EW, CNT=res.CNT), wide)
     if rank == 0 and args.dump:
-        np.savez(args.dump, LS=LSh.cpu().numpy(), EW=EWh.cpu().numpy(), CNT=CNTh.cpu().numpy())
+        np.savez(args.dump, LS=res.LS.cpu().numpy(), EW=res.EW.cpu().numpy(),
+                 CNT=res.CNT.cpu().numpy())
+    match, mom_exact = None, None
+    if args.full:
+        match, mom_exact = decile_match(args, res.M, res.L, panel, ms_host, J, skip, nb, world, dev,
+                                        sum(pipe.months) if pipe is not None else T_m)
 
     ms_per_step = 1000.0 * elapsed / args.steps
     units = N * total_days            # the whole panel (all ranks' date shards)
@@ -567,7 +643,7 @@ def main(argv=None):
     if rank == 0:
         alg_pipe = 8.0 * N * T_d + 17.0 * N * T_m + 8.0 * T_m * (nb + 1)   # SURVEY 8(d), per rank
         roofline = None
-        if world == 1:
+        if have_stages:
             me_ms = stage_ms[0] / args.steps
             if fused or tc:
                 kname = "k_signal_tc" if tc else "k_signal"
@@ -642,7 +718,7 @@ def main(argv=None):
                                   "frac": round(pipe_gbs / (HBM_PEAK_GBS * world), 4),
                                   "algorithmic_bytes_per_pass_per_gpu": alg_pipe},
             "stage_ms": ({k: round(v / args.steps, 4) for k, v in zip(stage_names, stage_ms)}
-                         if world == 1 else None),
+                         if have_stages else None),
             "decile_match_pct": match["pct"] if match else None,
             "mom_bit_exact_pct": mom_exact,
             "decile_check": match["sample"] if match else None,
@@ -650,7 +726,7 @@ def main(argv=None):
             # context only (not measured by this run): the reference's own pandas path
             "reference_pandas": REFERENCE_PANDAS,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_assets, T_d, cfg["start"])
         print(json.dumps(out), flush=True)
     dist_close()
@@ -964,19 +1040,33 @@ def sweep_main(args):
         graph = None
         elapsed, out = timed(step)
     elapsed = allreduce_host([elapsed], dist.ReduceOp.MAX if world > 1 else None, dev)[0]
-    ts.on = True
-    for _ in range(args.steps):
-        (step_defer if defer else step)()
-    torch.cuda.synchronize()
-    ts.on = False
-    stages = ts.stage_report(args.steps)
+    stages = None
+    if args.full:   # per-stage device times and algorithmic bytes: an instrumented, untimed pass
+        ts.on = True
+        for _ in range(args.steps):
+            (step_defer if defer else step)()
+        torch.cuda.synchronize()
+        ts.on = False
+        stages = ts.stage_report(args.steps)
     line = None
     if rank == 0:
-        dom = max(stages.items(), key=lambda kv: kv[1][0])
-        dname, (dms, dbytes) = dom
-        ach = dbytes / (dms * 1e-3) / 1e9
-        alg_step = sum(v[1] for v in stages.values())
         ms_step = 1000.0 * elapsed / args.steps
+        roofline = pipeline_roofline = None
+        if stages:
+            dom = max(stages.items(), key=lambda kv: kv[1][0])
+            dname, (dms, dbytes) = dom
+            ach = dbytes / (dms * 1e-3) / 1e9
+            alg_step = sum(v[1] for v in stages.values())
+            roofline = {"bound": "hbm", "kernel": dname, "achieved": round(ach, 1),
+                        "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
+                        "traffic": sweep_traffic(args.config, N, T_d, dname),
+                        **sweep_profile(args.config, N, T_d, dname, dbytes),
+                        "algorithmic_bytes_per_step": dbytes,
+                        "avg_ms_per_step": round(dms, 4)}
+            pipeline_roofline = {"bound": "hbm", "achieved": round(alg_step / (ms_step * 1e-3) / 1e9, 1),
+                                 "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                 "frac": round(alg_step / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                 "algorithmic_bytes_per_step_rank0": alg_step}
         res = out.cpu().numpy()
         res_summary = {f: float(np.nanmean(res[..., i])) for i, f in enumerate(csmom.SUMMARY_FIELDS)}
         line = {
@@ -993,31 +1083,25 @@ def sweep_main(args):
                        "strategies": S, "panels": n_panels, "weighting": "value" if args.config == "c3" else "equal",
                        "costs": "spread/2 + 0.1*vol*sqrt(size/ADV), AUM 1e8" if args.config == "c3" else "spread/2",
                        "parallelism": f"{'panel' if args.config == 'c5' else 'strategy'}-shard x{world}"},
-            "roofline": {"bound": "hbm", "kernel": dname, "achieved": round(ach, 1),
-                         "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(ach / HBM_PEAK_GBS, 4),
-                         "traffic": sweep_traffic(args.config, N, T_d, dname),
-                         **sweep_profile(args.config, N, T_d, dname, dbytes),
-                         "algorithmic_bytes_per_step": dbytes,
-                         "avg_ms_per_step": round(dms, 4)},
-            "pipeline_roofline": {"bound": "hbm", "achieved": round(alg_step / (ms_step * 1e-3) / 1e9, 1),
-                                  "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                                  "frac": round(alg_step / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                  "algorithmic_bytes_per_step_rank0": alg_step},
-            "stage_ms": {k: round(v[0], 4) for k, v in stages.items()},
+            "roofline": roofline,
+            "pipeline_roofline": pipeline_roofline,
+            "stage_ms": {k: round(v[0], 4) for k, v in stages.items()} if stages else None,
             "hipgraph": graph is not None,
             "result_means": res_summary,
             "cpu_baseline": None,
         }
-        if not args.no_oracle_mom:
+        if args.full and not args.no_oracle_mom:
             line["decile_match"] = sweep_decile_match(args.config, eng,
                                                       PM=PM if args.config == "c3" else None,
                                                       R0=R0 if args.config == "c5" else None)
             line["decile_match_pct"] = line["decile_match"]["decile_match_pct"]
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_sweep(args.config, 1500 if args.config == "c3" else 1000,
                                                       T_d, cfg["start"])
         if args.dump:
             np.savez(args.dump, table=res)
+        if args.dump_outputs:   # the summary table the last timed step returned
+            dump_outputs(args.dump_outputs, dict(table=out))
         print(json.dumps(line), flush=True)
     dist_close()
     return line

@@ -3,7 +3,7 @@
 # under its own time limit, and the run stops at the first failing step (no retries):
 #   tests[=<pytest -k expr>]   pytest -m gpu (one process), log gpurun_out/gpu_tests.log
 #   smoke                      __graft_entry__.smoke(), log gpurun_out/smoke.log
-#   bench=<cfg>[,arg,arg...]   python bench.py --config <cfg> [args], log gpurun_out/bench_<cfg>_<step#>.log
+#   bench=<cfg>[,arg,arg...]   python bench.py --config <cfg> --full [args], log bench_<cfg>_<step#>.log (same folder)
 #   trace=<cfg>[,arg...]       rocprofv3 --kernel-trace --stats of bench.py, gpurun_out/trace_<cfg>_<step#>.kernel_stats.csv
 #   profile=<cfg>              scripts/profile.sh <tag> <cfg> <head> (tag / head from $TAG / $HEAD_SHA)
 #   py=<script>[,arg...]       python <script> [args], log gpurun_out/py_<name>.log
@@ -32,7 +32,7 @@ for step in "$@"; do
     bench)
       cfg="${args%% *}"; rest="${args#"$cfg"}"
       log="gpurun_out/bench_${cfg}_${idx}.log"
-      timeout -k 10 600 python -u bench.py --config $cfg $rest > "$log" 2>&1
+      timeout -k 10 600 python -u bench.py --config $cfg --full $rest > "$log" 2>&1
       rc=$?; grep -o '"value": [0-9.e+]*\|"ms_per_step": [0-9.]*\|"frac": [0-9.]*\|"stage_ms": {[^}]*}\|"decile_match_pct": [0-9.]*' "$log" | tr '\n' ' '; echo ;;
     trace)
       cfg="${args%% *}"; rest="${args#"$cfg"}"

@@ -27,7 +27,7 @@ case "$CFG" in
       STAGE="--stage portfolio(k_cohort+k_turnover+k_overlap+k_ls)=k_label_sort,k_label_sort_legs_ew,k_cohort_seg,k_cohort_lds,k_cohort,k_fw_fold,k_turn_prep,k_turnover,k_overlap,k_overlap_rows,k_ls,k_ls_wide,k_ls_flags,k_ls_rows,k_turnover_vwg,k_turnover_ew_mask" ;;
   *) echo "unknown config $CFG"; exit 2 ;;
 esac
-BENCH="bench.py --gpus 1 --config $CFG --no-cpu-baseline $EXTRA"
+BENCH="bench.py --gpus 1 --config $CFG --full --no-cpu-baseline $EXTRA"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -o run -- python3 $BENCH $RUN > "$OUT/trace.log" 2>&1
 rc=$?; grep -h '"metric"' "$OUT/trace.log" | cut -c1-300; [ $rc -eq 0 ] || { tail -5 "$OUT/trace.log"; echo "FATAL trace rc=$rc"; exit $rc; }
 timeout -s KILL 240 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/pmc_fetch" -o run -- python3 $BENCH $PMC > "$OUT/pmc_fetch.log" 2>&1

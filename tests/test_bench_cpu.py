@@ -58,6 +58,47 @@ def test_make_device_panel_past_pandas_range():
     assert len(pan.month_end) == len(pan.month_start_host) - 1
 
 
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs' writer: small arrays whole, the wide ones on one fixed seeded column sample
+    that keeps the files within 64 MB, everything finite (a float array's NaN / inf cells are
+    written as 0 and coded in <name>_nonfinite.npy) and the same from call to call."""
+    import torch
+    import bench
+    assert bench.parse([]).full is False and bench.parse([]).dump_outputs is None
+    assert bench.parse(["--full", "--dump-outputs", "x"]).dump_outputs == "x"
+    rows, N = 461, 100_000                       # C4's months x assets (int8 keeps this small)
+    L = (torch.arange(rows * N, dtype=torch.int64) % 11 - 1).to(torch.int8).reshape(rows, N)
+    LS = torch.arange(rows, dtype=torch.float64)
+    LS[:3] = torch.tensor([float("nan"), float("inf"), float("-inf")], dtype=torch.float64)
+    small = dict(LS=LS, CNT=torch.ones(rows, 10, dtype=torch.int32))
+    M = L.to(torch.float64)
+    M[L < 0] = float("nan")
+    wide = dict(M=M, NR=M, L=L)
+    a, b = tmp_path / "a", tmp_path / "b" / "nested"
+    bench.dump_outputs(a, small, wide)
+    bench.dump_outputs(b, small, wide)
+    fa = {f.name: np.load(f) for f in a.iterdir()}
+    fb = {f.name: np.load(f) for f in b.iterdir()}
+    assert sorted(fa) == ["CNT.npy", "L.npy", "LS.npy", "LS_nonfinite.npy", "M.npy",
+                          "M_nonfinite.npy", "NR.npy", "NR_nonfinite.npy", "columns.npy"]
+    assert sorted(fb) == sorted(fa) and all(np.array_equal(fa[k], fb[k]) for k in fa)
+    assert all(v.dtype == (np.float32 if "_nonfinite" in k else np.float64) for k, v in fa.items())
+    assert all(np.isfinite(v).all() for v in fa.values())
+    assert sum(v.nbytes for v in fa.values()) <= 64 << 20
+    cols = fa["columns.npy"].astype(np.int64)
+    assert 1000 < len(cols) < N and (np.diff(cols) > 0).all() and cols[-1] < N
+    assert np.array_equal(fa["L.npy"], L.numpy()[:, cols].astype(np.float64))
+    assert np.array_equal(fa["LS.npy"][3:], np.arange(3.0, rows)) and not fa["LS.npy"][:3].any()
+    assert fa["LS_nonfinite.npy"].tolist() == [1.0, 2.0, 3.0] + [0.0] * (rows - 3)
+    Lc = L.numpy()[:, cols]
+    assert np.array_equal(fa["M_nonfinite.npy"], (Lc < 0).astype(np.float32))
+    assert np.array_equal(fa["M.npy"], np.where(Lc < 0, 0.0, Lc))
+    # a narrow panel is written whole
+    bench.dump_outputs(tmp_path / "c", {}, dict(M=M[:, :50]))
+    assert np.array_equal(np.load(tmp_path / "c" / "columns.npy"), np.arange(50.0))
+    assert np.load(tmp_path / "c" / "M.npy").shape == (rows, 50)
+
+
 def test_gpus_n_self_launches(monkeypatch):
     """Without a torchrun environment `--gpus N > 1` hands the argv to spawn_workers (the parent
     imports no torch); with WORLD_SIZE set (a worker) it runs the bench itself."""

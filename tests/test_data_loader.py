@@ -1,17 +1,16 @@
 """CPU: the offline daily-CSV loader (src/data_io.py:23-73,131-180 rules) and the long -> dense
 ingestion.  Pinned by the real-data fixture (made by the reference's own fetch_daily over its
 cached CSVs): the loader must reproduce that dense panel bit for bit and drop AAPL (the
-3-row-header file) exactly as the reference does.  The reference's data/ directory is read
-only when it is present (this container); the GPU box never runs these tests."""
-from pathlib import Path
+3-row-header file) exactly as the reference does.  Those cached CSVs are stored unchanged in
+tests/golden/daily_csv.tar.xz and unpacked into a temporary directory."""
+import tarfile
 
 import numpy as np
 import pandas as pd
-import pytest
 
-from conftest import bits_equal, load_golden
+from conftest import GOLDEN, bits_equal, load_golden
 
-REF_DATA = Path("/root/reference/data")
+REF_DATA = GOLDEN / "daily_csv.tar.xz"
 TICKERS = ["AAPL", "MSFT", "AMZN", "GOOGL", "NVDA", "TSLA", "META", "JPM", "BAC", "WMT", "PG",
            "KO", "DIS", "CSCO", "ORCL", "INTC", "AMD", "NFLX", "C", "GS"]  # run_demo.py:15-16
 
@@ -60,11 +59,15 @@ def test_reference_call_signature(tmp_path, monkeypatch, capsys):
     assert list(D.fetch_daily([], verbose=False).columns) == D.DAILY_COLUMNS
 
 
-@pytest.mark.skipif(not REF_DATA.exists(), reason="reference data/ not present")
-def test_loader_reproduces_reference_panel():
+def test_loader_reproduces_reference_panel(tmp_path):
     import csmom.data as D
     z = load_golden("real_data")
-    panel = D.load_daily_panel(TICKERS, str(REF_DATA))
+    with tarfile.open(REF_DATA) as tar:
+        names = tar.getnames()
+        assert sorted(names) == sorted(f"{t}_daily.csv" for t in TICKERS)   # plain names only
+        for n in names:
+            (tmp_path / n).write_bytes(tar.extractfile(n).read())
+    panel = D.load_daily_panel(TICKERS, str(tmp_path))
     assert list(panel.tickers) == list(z["tickers"])           # AAPL dropped, sorted
     assert np.array_equal(panel.days.asi8, z["day_ns"])
     assert np.array_equal(panel.month_start, z["month_start"])

@@ -121,7 +121,7 @@ def test_bench_c4_self_launch_strong_scaling(engine, tmp_path):
     N, DAYS, SEED = 40_000, 2_200, 4
     dump = tmp_path / "c4s.npz"
     line = _self_launch(["--gpus", "2", "--backend", "gloo", "--assets", str(N), "--days",
-                         str(DAYS), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                         str(DAYS), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                          "--seed", str(SEED), "--dump", str(dump)])
     assert line["n_gpus"] == 2 and line["decile_match_pct"] == 100.0
     assert line["scaling"] == "strong" and line["config"]["bdays"] == DAYS
@@ -143,7 +143,7 @@ def test_bench_c4_two_ranks_gloo(engine, tmp_path):
     N, DAYS, SEED = 40_000, 1_100, 4
     dump = tmp_path / "c4.npz"
     line = _spawn_bench(["--gpus", "2", "--backend", "gloo", "--assets", str(N), "--days",
-                         str(DAYS), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                         str(DAYS), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
                          "--seed", str(SEED), "--dump", str(dump), "--scaling", "weak",
                          "--shard-mode", "fused"])
     assert line["n_gpus"] == 2 and line["decile_match_pct"] == 100.0
