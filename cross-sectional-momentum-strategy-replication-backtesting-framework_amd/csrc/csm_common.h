@@ -7,6 +7,7 @@
 #include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <string.h>
 
 #include "../../include/csmom.h"
 
@@ -76,6 +77,25 @@ static inline int prep(csm_ctx* c) {
 }
 
 static inline bool aligned16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+
+// One csm_tune knob: its key, the variable it sets and the values it accepts.  tune_set stores
+// value into the table's knob named key; CSM_E_INVAL for a NULL or unknown key or a value the
+// knob does not accept.
+struct TuneKnob {
+  const char* key;
+  int* var;
+  bool (*ok)(int);
+};
+template <size_t n>
+static inline int tune_set(const TuneKnob (&tab)[n], const char* key, int value) {
+  if (!key) return CSM_E_INVAL;
+  for (const TuneKnob& k : tab)
+    if (!strcmp(key, k.key) && k.ok(value)) {
+      *k.var = value;
+      return CSM_OK;
+    }
+  return CSM_E_INVAL;
+}
 
 // Whether the context's stream is being captured into a hipGraph.  Context-owned buffers are
 // baked into a captured graph by address, so they are never (re)allocated while capturing.

@@ -766,10 +766,6 @@ __device__ __forceinline__ void scan_shadow(ScanLane& s, double x, int m, double
   }
 }
 
-#ifdef SIG_HIST
-__device__ uint32_t* g_sig_hist;   // A/B build only: csm_signal_ids' per-month id histogram
-#endif
-
 #define HALO_WALK 24   // a business month's day rows in one batch of loads
 #define HALO_MAXG 64
 
@@ -1054,17 +1050,6 @@ __global__ __launch_bounds__(64 * BW) void k_signal(
           mom[c] = scan_step(sl[c], pm[c], m, ring_lds + VEC * tid + c, RS, W, J, N, a0 + c, R, M, NR);
       }
       if (IDS) {   // fixed-map bucket ids for the decile pass (csm_signal_ids)
-#ifdef SIG_HIST
-        // A/B only (verdict r05 #4): the cost of a per-month id histogram built here by
-        // integer atomics ([T_m][8192] u32, the decile pass's bucket of each ranked id)
-        if (g_sig_hist) {
-#pragma unroll
-          for (int c = 0; c < VEC; ++c) {
-            const uint32_t id = csm_fid(mom[c]);
-            if (id != CSM_FB_NAN) atomicAdd(g_sig_hist + (int64_t)m * 8192 + (id >> 3), 1u);
-          }
-        }
-#endif
         if (VEC == 2)
           *reinterpret_cast<uint32_t*>(IDS + (int64_t)m * N + a0) =
               csm_fid(mom[0]) | (csm_fid(mom[VEC - 1]) << 16);
@@ -1512,13 +1497,6 @@ __global__ __launch_bounds__(256) void k_fold_carry(const double* __restrict__ s
 #ifndef TC_REC2
 #define TC_REC2 1        // the record's forward and backward fields by the two wave halves
 #endif
-// -DTC_TIMING (experiment builds, scripts/build_variant.py): per-workgroup phase stamps
-// (wall clock, 100 MHz) in 8 u64 words per ticket after the records (workspace grows)
-#ifdef TC_TIMING
-#define TC_STAMP(k) do { if (tid == 0) stamp[k] = wall_clock64(); } while (0)
-#else
-#define TC_STAMP(k) do { } while (0)
-#endif
 
 typedef __attribute__((address_space(1))) unsigned int tc_gu32;
 typedef __attribute__((address_space(1))) unsigned long long tc_gu64;
@@ -1784,10 +1762,6 @@ __global__ __launch_bounds__(TC_THREADS, TC_LBW) void k_signal_tc(
   const int tid = threadIdx.x;
   const int W = WR > 0 ? WR : J + skip, T = W + 1, SR = SUM_SCALARS + T + 1;
   const unsigned total = (unsigned)G * (unsigned)nbx;
-#ifdef TC_TIMING
-  unsigned long long stamp[8];
-#endif
-  TC_STAMP(0);
   if (tid == 0) s_t = (int)atomicInc(sync, total - 1u);   // wraps to 0 after the last ticket
   __syncthreads();
   const int t = s_t, g = t / nbx, x = t - g * nbx;
@@ -1839,7 +1813,6 @@ __global__ __launch_bounds__(TC_THREADS, TC_LBW) void k_signal_tc(
     *reinterpret_cast<double2*>(pmL + (m - m0) * RS + lm) = make_double2(pm[0], pm[1]);
   }
   __syncthreads();
-  TC_STAMP(1);
 
   // ---- 2. this chunk's record (k_shard_summary_chunked's fields + last present month) ----
   const int64_t hstride = (int64_t)nbx * SR * RS;   // chunk stride of a column's records
@@ -1912,7 +1885,6 @@ __global__ __launch_bounds__(TC_THREADS, TC_LBW) void k_signal_tc(
   if (tid == 0)
     __hip_atomic_store((tc_gu32*)(sync + TC_SYNC0 + (int64_t)g * nbx + x), 1u, __ATOMIC_RELAXED,
                        __HIP_MEMORY_SCOPE_AGENT);
-  TC_STAMP(2);
 
   // ---- 3. wait for the records of chunks 0..g-1 of this column ----
   if (g > 0) {
@@ -1940,7 +1912,6 @@ __global__ __launch_bounds__(TC_THREADS, TC_LBW) void k_signal_tc(
     }
     __syncthreads();
   }
-  TC_STAMP(3);
 
   // ---- 4. the scan state at month m0 ----
   ScanLane sl;
@@ -1964,7 +1935,6 @@ __global__ __launch_bounds__(TC_THREADS, TC_LBW) void k_signal_tc(
       for (int k = 0; k < W; ++k) rl[k * RS] = NaN;
     }
   }
-  TC_STAMP(4);
 
   // ---- 5. scan the chunk's months from LDS (the next month's price read a step ahead) ----
   if (live) {
@@ -1982,16 +1952,6 @@ __global__ __launch_bounds__(TC_THREADS, TC_LBW) void k_signal_tc(
 
   // ---- 6. the last workgroup out zeroes the flags for the next launch ----
   __syncthreads();
-  TC_STAMP(5);
-#ifdef TC_TIMING
-  if (tid == 0) {
-    stamp[6] = (unsigned long long)g;
-    stamp[7] = (unsigned long long)x;
-    unsigned long long* o = reinterpret_cast<unsigned long long*>(
-        rec + (int64_t)total * SR * RS) + (int64_t)t * 8;
-    for (int k = 0; k < 8; ++k) o[k] = stamp[k];
-  }
-#endif
   if (tid == 0) s_last = atomicInc(sync + 1, total - 1u) == total - 1u;
   __syncthreads();
   if (s_last)
@@ -2571,7 +2531,7 @@ static int g_tune_dec_merge = 1;
 // one-workgroup-per-row pass | 1 always split | 0 never.  Same labels and counts; decile means in
 // another fixed order
 static int g_tune_dec_split = 2;
-static int64_t g_tune_dec_split_cells = SPLIT_CELLS;   // cells per split-sweep chunk
+static int g_tune_dec_split_cells = SPLIT_CELLS;   // cells per split-sweep chunk
 // the split sweep: 0 the two-workgroups-per-CU variant (no prefetch) | 1 the prefetching one
 // workgroup per CU | 2 prefetch when the launch has no more (chunk, date) pairs than CUs.
 // C4 rank rehearsals, deciles_ids ms: 4-way 0.1162 / 0.1338 / 0.1165, 8-way 0.0998 / 0.1019 /
@@ -2581,10 +2541,26 @@ static int g_tune_dec_split_pf = 0;
 // per lane | 0 the shared-memory ring (max(J) + skip > 16 always takes it)
 static int g_tune_mj_reg = 2;
 // rows with at most this many assets take the narrow-row decile kernels
-static int64_t g_tune_dec_narrow_max = 16384;
+static int g_tune_dec_narrow_max = 16384;
 // k_signal_tc: polling trips a waiting workgroup makes before it gives up and marks the launch
 // (0: give up at once -- only the tests of the failure report set it)
-static unsigned g_tune_tc_spins = TC_SPINS;
+static int g_tune_tc_spins = TC_SPINS;
+
+// this file's knobs; the portfolio's are in portfolio.hip's table
+static const TuneKnob g_knobs[] = {
+    {"signal_vec", &g_tune_signal_vec, [](int v) { return v == 1 || v == 2; }},
+    {"signal_bwf", &g_tune_signal_bwf, [](int v) { return v == 0 || v == 1 || v == 4; }},
+    {"signal_j12", &g_tune_signal_j12, [](int v) { return v == 0 || v == 1; }},
+    {"cols_wg", &g_tune_cols_wg, [](int v) { return v == 0 || v == 1; }},
+    {"dec_merge", &g_tune_dec_merge, [](int v) { return v == 0 || v == 1; }},
+    {"mj_reg", &g_tune_mj_reg, [](int v) { return v >= 0 && v <= 2; }},
+    {"dec_narrow_max", &g_tune_dec_narrow_max, [](int v) { return v >= 0; }},
+    {"dec_split", &g_tune_dec_split, [](int v) { return v >= 0 && v <= 2; }},
+    {"dec_split_pf", &g_tune_dec_split_pf, [](int v) { return v >= 0 && v <= 2; }},
+    {"tc_spins", &g_tune_tc_spins, [](int v) { return v >= 0; }},
+    {"dec_split_cells", &g_tune_dec_split_cells,
+     [](int v) { return v >= SPLIT_TRIP && v % SPLIT_TRIP == 0; }},
+};
 
 extern "C" {
 
@@ -2594,31 +2570,12 @@ int csm_tune_portfolio(const char* key, int value);  // portfolio.hip
 int csm_tune_ptr_portfolio(const char* key, void* p);  // portfolio.hip
 
 int csm_tune(const char* key, int value) {
-  if (!key) return CSM_E_INVAL;
-  if (!strcmp(key, "cohort_lds") || !strcmp(key, "cohort_seg") || !strcmp(key, "turn_want") ||
-      !strcmp(key, "overlap_rows") || !strcmp(key, "turn_gen_grid") || !strcmp(key, "gen_reset") ||
-      !strcmp(key, "turn_vwg") || !strcmp(key, "turn_mask") || !strcmp(key, "ls_opt"))
-    return csm_tune_portfolio(key, value);
-  if (!strcmp(key, "signal_vec") && (value == 1 || value == 2)) { g_tune_signal_vec = value; return CSM_OK; }
-  if (!strcmp(key, "signal_bwf") && (value == 0 || value == 1 || value == 4)) { g_tune_signal_bwf = value; return CSM_OK; }
-  if (!strcmp(key, "signal_j12") && (value == 0 || value == 1)) { g_tune_signal_j12 = value; return CSM_OK; }
-  if (!strcmp(key, "cols_wg") && (value == 0 || value == 1)) { g_tune_cols_wg = value; return CSM_OK; }
-  if (!strcmp(key, "dec_merge") && (value == 0 || value == 1)) { g_tune_dec_merge = value; return CSM_OK; }
-  if (!strcmp(key, "mj_reg") && value >= 0 && value <= 2) { g_tune_mj_reg = value; return CSM_OK; }
-  if (!strcmp(key, "dec_narrow_max") && value >= 0) { g_tune_dec_narrow_max = value; return CSM_OK; }
-  if (!strcmp(key, "dec_split") && value >= 0 && value <= 2) { g_tune_dec_split = value; return CSM_OK; }
-  if (!strcmp(key, "dec_split_pf") && value >= 0 && value <= 2) { g_tune_dec_split_pf = value; return CSM_OK; }
-  if (!strcmp(key, "tc_spins") && value >= 0) { g_tune_tc_spins = (unsigned)value; return CSM_OK; }
-  if (!strcmp(key, "dec_split_cells") && value >= SPLIT_TRIP && value % SPLIT_TRIP == 0) {
-    g_tune_dec_split_cells = value;
-    return CSM_OK;
-  }
-  return CSM_E_INVAL;
+  if (tune_set(g_knobs, key, value) == CSM_OK) return CSM_OK;
+  return csm_tune_portfolio(key, value);
 }
 
 int csm_tune_ptr(const char* key, void* p) {
-  if (!key) return CSM_E_INVAL;
-  if (!strcmp(key, "dec_timing")) { g_dec_timing = (int64_t*)p; return CSM_OK; }
+  if (key && !strcmp(key, "dec_timing")) { g_dec_timing = (int64_t*)p; return CSM_OK; }
   return csm_tune_ptr_portfolio(key, p);
 }
 
@@ -2897,20 +2854,6 @@ int csm_signal_ids(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
     return set_err(ctx, CSM_E_INVAL, "csm_signal_ids: ids must be non-NULL and 8-B aligned, N %% 4 == 0 "
                    "(N=%lld)", (long long)N);
   (void)min_month_days;   // kept in the ABI (host hint for fixed day batches; no kernel uses it)
-#ifdef SIG_HIST
-  {   // A/B build only: a zeroed [T_m][8192] histogram per launch
-    static uint32_t* hist = nullptr;
-    static int64_t cap = 0;
-    const int64_t need = (int64_t)T_m * 8192;
-    if (need > cap) {
-      if (hist) hipFree(hist);
-      HIP_CHECK(ctx, hipMalloc(&hist, need * 4));
-      cap = need;
-      HIP_CHECK(ctx, hipMemcpyToSymbol(HIP_SYMBOL(g_sig_hist), &hist, sizeof(hist)));
-    }
-    HIP_CHECK(ctx, hipMemsetAsync(hist, 0, need * 4, ctx->stream));
-  }
-#endif
   return signal_launch(ctx, "csm_signal_ids", P, T_d, N, month_start, T_m, max_month_days, J,
                        skip, PM, R, M, NR, nullptr, nullptr, nullptr, false, ids);
 }
@@ -3613,11 +3556,7 @@ int64_t csm_signal_chunked_workspace(int32_t T_m, int64_t N, int32_t J, int32_t 
   if (N <= 0 || C < 1 || J < 1 || skip < 0) return 0;
   (void)T_m;
   const int64_t nbx = (N + TC_COLS - 1) / TC_COLS, SR = SUM_SCALARS + J + skip + 2;
-  int64_t b = tc_sync_bytes(C, (int)nbx) + (int64_t)C * nbx * SR * TC_COLS * (int64_t)sizeof(double);
-#ifdef TC_TIMING
-  b += (int64_t)C * nbx * 64;
-#endif
-  return b;
+  return tc_sync_bytes(C, (int)nbx) + (int64_t)C * nbx * SR * TC_COLS * (int64_t)sizeof(double);
 }
 
 int csm_signal_chunked(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,

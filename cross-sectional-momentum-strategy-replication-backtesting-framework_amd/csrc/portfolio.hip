@@ -91,7 +91,7 @@ static PanAddr pan_grouped(int G, int Bg, int T_m, int64_t N, bool shared_nr = f
 template <int NB, bool VW>
 __global__ __launch_bounds__(PF_THREADS) void k_cohort(
     const int8_t* __restrict__ L, const double* __restrict__ NR, const double* __restrict__ W,
-    int T_m, int B, int64_t N, int K, int C, int64_t CH, int kpar, double* __restrict__ SWRp,
+    int T_m, int B, int64_t N, int K, int C, int64_t CH, double* __restrict__ SWRp,
     double* __restrict__ SWp, double* __restrict__ FWp, PanAddr pa) {
   __shared__ double red[PF_WAVES][2 * NB + 2];
   const int c = (int)(blockIdx.x % (unsigned)C);
@@ -101,8 +101,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_cohort(
   const int64_t a0 = (int64_t)c * CH;
   const int64_t a1 = a0 + CH < N ? a0 + CH : N;
   const int64_t rt = pa.nrow(t, b);   // next_ret row of month t
-  const int k_lo = kpar ? (int)blockIdx.z : 0, k_hi = kpar ? k_lo + 1 : K;
-  for (int k = k_lo; k < k_hi; ++k) {
+  for (int k = 0; k < K; ++k) {
     const int s = t - k;
     const int64_t ob = (((int64_t)tb * K + k) * C + c) * NB;
     if (s < 0) {
@@ -425,14 +424,11 @@ __device__ __forceinline__ uint32_t byte_eq0(uint32_t z) {   // 0x80 in each byt
 // not depend on the order).
 // LSO: prefix ranks by v_mbcnt (fewer VALU operations per label word than the popcount of the
 // masked ballot; the same values)
-// LS_STAGE: a row whose two legs hold at most LS_CAP ids (sentinels included) builds its segment
+// Staged store: a row whose two legs hold at most LS_CAP ids (sentinels included) builds its segment
 // in the wave's LDS slice and stores it once, as 8-byte words of consecutive positions, instead
 // of each lane storing its own 2-byte ids a few positions apart (those stores were 280 of 1020
 // us per C5 batch, -DLS_NOSTORE timing); larger rows store directly.  The same ids at the same
 // positions.
-#ifndef LS_STAGE
-#define LS_STAGE 1
-#endif
 #define LS_CAP 2048
 template <int NB, bool LSO = false>
 __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
@@ -472,7 +468,6 @@ __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
   const int rb = (nb0 + 3) & ~3, rt = (nt0 + 3) & ~3;
   uint16_t* Pr = PERM + row * PS;
   if (lane <= NB) OFF[row * (NB + 1) + lane] = lane == 0 ? 0 : (lane < NB ? rb : rb + rt);
-#if LS_STAGE
   __shared__ __attribute__((aligned(16))) uint16_t stg[PF_WAVES][LS_CAP];
   uint16_t* sp = stg[threadIdx.x >> 6];
   const bool staged = rb + rt <= LS_CAP;   // (wave-uniform)
@@ -483,10 +478,6 @@ __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
     if (lane < rb - nb0) Pr[nb0 + lane] = (uint16_t)N;
     if (lane < rt - nt0) Pr[rb + nt0 + lane] = (uint16_t)N;
   }
-#else
-  if (lane < rb - nb0) Pr[nb0 + lane] = (uint16_t)N;               // sentinel ids
-  if (lane < rt - nt0) Pr[rb + nt0 + lane] = (uint16_t)N;
-#endif
   for (int i = lane; i < 2 * C; i += 64) {   // leg totals in chunk 0 (leg 0 = top), zeros elsewhere
     const int c = i >> 1, leg = i & 1;
     FWp[(row * C + c) * 2 + leg] = c == 0 ? (double)(leg == 0 ? nt0 : nb0) : 0.0;
@@ -525,7 +516,6 @@ __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
         LM[(row * 2 + 1) * nwm + w] = pw_b;
       }
     }
-#if LS_STAGE
     if (staged) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {   // lane-major then byte order = ascending asset id
@@ -533,9 +523,7 @@ __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
         if ((eb >> (8 * e + 7)) & 1u) sp[bb++] = a;
         if ((et >> (8 * e + 7)) & 1u) sp[bt++] = a;
       }
-    } else
-#endif
-    {
+    } else {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {   // lane-major then byte order = ascending asset id
         const uint16_t a = (uint16_t)(4 * wi + e);
@@ -546,7 +534,6 @@ __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
     pb += totb;
     pt += tott;
   }
-#if LS_STAGE
   if (staged) {   // the whole segment out: 4 ids per 8-byte store, consecutive lanes
     __builtin_amdgcn_wave_barrier();
     const int nw8 = (rb + rt) >> 2;
@@ -555,7 +542,6 @@ __global__ __launch_bounds__(PF_THREADS) void k_label_sort_legs_ew(
     for (int i = lane; i < nw8; i += 64) d8[i] = s8[i];
     __builtin_amdgcn_wave_barrier();
   }
-#endif
 }
 
 // 16-lane groups, one (age, decile) segment per group at a time: a short reduction (4 steps)
@@ -580,9 +566,6 @@ struct SegJ {
   double* SW[SEG_MAXJ];
   int n;
 };
-#ifndef SEG_PANEL_MAJOR
-#define SEG_PANEL_MAJOR 1
-#endif
 template <int NB, bool VW, bool LEGS = false>
 __global__ __launch_bounds__(PF_THREADS) void k_cohort_seg(
     const double* __restrict__ NR, SegJ sj, const double* __restrict__ WSRT, int T_m, int B,
@@ -608,21 +591,16 @@ __global__ __launch_bounds__(PF_THREADS) void k_cohort_seg(
   int t;
   if (xcd) {   // C == 1
     // XCD-aware order: workgroups go round-robin to the 8 XCDs, so workgroup id -> (t, b)
-    // keeps panel b on XCD b % 8.  SEG_PANEL_MAJOR (default): an XCD's workgroups take one
-    // panel's months in order, then its next panel, so the K formation rows (member ids) a
-    // month re-reads were read by the months just before it, in that XCD's L2 (else: the
-    // XCD's panels for one month, then the next month -- the L2 then also holds the return
-    // rows of ~Bx other panels between two uses of a formation row).
+    // keeps panel b on XCD b % 8.  Panel-major: an XCD's workgroups take one panel's months
+    // in order, then its next panel, so the K formation rows (member ids) a month re-reads
+    // were read by the months just before it, in that XCD's L2 (month-major -- the XCD's
+    // panels for one month, then the next month -- left the return rows of ~Bx other panels
+    // in the L2 between two uses of a formation row, and measured slower).
     const int id = (int)blockIdx.x, x = id & 7, j = id >> 3;
     const int Bx = (B + 7) >> 3;
-#if SEG_PANEL_MAJOR
     const int bj = j / T_m;
     t = j - bj * T_m;
     const int b = x + 8 * bj;
-#else
-    t = j / Bx;
-    const int b = x + 8 * (j - t * Bx);
-#endif
     if (b >= B || t >= T_m || j >= Bx * T_m) return;
     tb = (int64_t)t * B + b;
   } else {
@@ -910,12 +888,9 @@ __global__ __launch_bounds__(TP_THREADS) void k_turn_prep(const double* __restri
   TPm[tb] = m;
 }
 
-// TO_GEN_TAB: the general equal-weight rows' non-full legs from per-row tables of the ages
+// The general equal-weight rows' non-full legs come from per-row tables of the ages
 // 0..TB-1 / 1..TB (TB = TO_GEN_TB) plus a walk over the ages >= TB, instead of a walk over every
 // age (the same sums)
-#ifndef TO_GEN_TAB
-#define TO_GEN_TAB 1
-#endif
 #ifndef TO_GEN_TB
 #define TO_GEN_TB 8
 #endif
@@ -1129,7 +1104,6 @@ __device__ __forceinline__ void turnover_body(
       for (int q = 0; q < nq; ++q)
         fullm |= (full[q][0] ? 1u : 0u) << (2 * q) | (full[q][1] ? 1u : 0u) << (2 * q + 1);
       const bool anyfree = fullm != (1u << (2 * nq)) - 1u;
-#if TO_GEN_TAB
       // legs that are not full take x1 / x0 from per-row tables for the ages 0..TB-1 / 1..TB
       // (each entry the ascending sum of inv over its member ages: the walk's own additions,
       // the +0.0 of a non-member age being exact for these non-negative sums), and walk only the
@@ -1148,7 +1122,6 @@ __device__ __forceinline__ void turnover_body(
         }
         __syncthreads();
       }
-#endif
       for (int64_t a4 = a0 + cw * tid; a4 < a1 && amask; a4 += cw * PF_THREADS) {
         uint32_t mt4[4] = {0, 0, 0, 0}, mb4[4] = {0, 0, 0, 0};
         if (cw == 4) {
@@ -1195,7 +1168,6 @@ __device__ __forceinline__ void turnover_body(
             sb[q] += e1 & e0;
           }
         }
-#if TO_GEN_TAB
         if (anyfree) {
           // x1 of the ages 0..TB-1 and x0 of the ages 1..TB from the tables; pairs with K_q <= TB
           // charged from them, cells and legs in order (each pair's terms in the walk's order)
@@ -1253,45 +1225,6 @@ __device__ __forceinline__ void turnover_body(
             }
           }
         }
-#else
-        if (anyfree) {
-          // legs that are not full: x1 = sum of inv over the member ages 0..K-1 (month t's
-          // window), x0 over 1..K (month t-1's), both ascending.  One walk over the ages for
-          // every (cell, leg) with inv read once per age (a broadcast): an age the cell is not
-          // in adds 0.0, exact for these non-negative sums, so x1 / x0 are the sums over the set
-          // bits in ascending order.  Pair q is charged at age K_q, cells and legs in order.
-          double sa[4][2], sz[4][2];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { sa[e][0] = sa[e][1] = 0.0; sz[e][0] = sz[e][1] = 0.0; }
-#pragma unroll 1
-          for (int j = 0; j <= kq; ++j) {
-            asm volatile("" ::: "memory");   // the factors are re-read (broadcasts), not held
-            const double iv0 = inv[0][j], iv1 = inv[1][j];
-            // pairs q with K_q == j are charged now: x1 = sa (ages < j), x0 = sz + v (ages 1..j)
-            uint32_t cq = 0;
-#pragma unroll
-            for (int q = 0; q < TO_MAXQ; ++q)
-              cq |= (q < nq && ks.K[q] == j) ? (3u << (2 * q)) & ~fullm : 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-#pragma unroll
-              for (int li = 0; li < 2; ++li) {
-                const uint32_t mm = li == 0 ? mt4[e] : mb4[e];
-                const double v = ((mm >> j) & 1u) ? (li == 0 ? iv0 : iv1) : 0.0;
-                if (cq && e < ne) {
-#pragma unroll
-                  for (int q = 0; q < TO_MAXQ; ++q)
-                    if ((cq >> (2 * q + li)) & 1u)
-                      charge(q, fabs(sa[e][li] * sk[q][li][0] - (sz[e][li] + v) * sk[q][li][1]),
-                             -1.0, 0.02);
-                }
-                sa[e][li] += v;
-                if (j >= 1) sz[e][li] += v;
-              }
-            }
-          }
-        }
-#endif
       }
     } else if constexpr (!BM) {
     // ages whose cohort is empty on both legs add 0.0 to every sum (inv 0.0) and make neither
@@ -1474,9 +1407,6 @@ __device__ __forceinline__ void turnover_body(
 // the same integers, so the TURN / COST partials are k_turnover's bits.  Rows that are not all
 // full go onto the general launch's work list as k_turnover's steady launch puts them.
 #define TM_WAVES 4
-#ifndef TM_EARLY
-#define TM_EARLY 1   // the row's loads issued together (and its counts reduced packed)
-#endif
 __global__ __launch_bounds__(64 * TM_WAVES) void k_turnover_ew_mask(
     const uint64_t* __restrict__ LM, int64_t nwm, int T_m, int B, int64_t N, KSet ks, int64_t CH,
     int Ct, double half_spread, double* __restrict__ TURNp, double* __restrict__ COSTp,
@@ -1489,8 +1419,8 @@ __global__ __launch_bounds__(64 * TM_WAVES) void k_turnover_ew_mask(
   const int c = bid % Ct, tb = bid / Ct;
   const int t = tb / B, b = tb - t * B;
   const int nq = ks.n;
-#if TM_EARLY
-  // every load of the row at once -- its mask, its factors (lane q < nq), the plane words of
+  // chunk c's cells [c CH, min(N, (c + 1) CH)): whole 256-cell groups, 4 words each (cells past
+  // N hold no member).  Every load of the row at once -- its mask, its factors (lane q < nq), the plane words of
   // months t and t - K_q (addresses clamped to month 0 for the rows the mask sends elsewhere:
   // those loads are discarded) -- instead of mask -> words -> factors, three round trips
   const uint32_t m = TPm[tb];
@@ -1590,75 +1520,6 @@ __global__ __launch_bounds__(64 * TM_WAVES) void k_turnover_ew_mask(
     TURNp[((int64_t)q * rows + tb) * Ct + c] = 0.5 * x;
     COSTp[((int64_t)q * rows + tb) * Ct + c] = x * half_spread;
   }
-#else
-  const uint32_t m = TPm[tb];
-  if (m & TP_EMPTY) return;   // k_turn_prep wrote its partials
-  const uint32_t need = (1u << (2 * nq)) - 1u;
-  if ((m & need) != need) {   // the general launch's row
-    if (gen_list && lane == 0) {
-      const int slot = atomicAdd(gen_count, 1);
-      if (slot < rows * Ct) gen_list[slot] = bid;
-    }
-    return;
-  }
-  // chunk c's cells [c CH, min(N, (c + 1) CH)): whole 256-cell groups, 4 words each (cells past
-  // N hold no member)
-  const int64_t w0 = (int64_t)c * CH / 64;
-  const int64_t a1 = (int64_t)(c + 1) * CH < N ? (int64_t)(c + 1) * CH : N;
-  const int64_t w1 = (a1 + 255) / 256 * 4;
-  const uint64_t* r1 = LM + (int64_t)tb * 2 * nwm;
-  uint32_t n1[2] = {0, 0}, n0[TO_MAXQ][2], nb[TO_MAXQ][2];
-#pragma unroll
-  for (int q = 0; q < TO_MAXQ; ++q) n0[q][0] = n0[q][1] = nb[q][0] = nb[q][1] = 0;
-  for (int64_t w = w0 + lane; w < w1; w += 64) {
-    uint64_t x1[2], x0[TO_MAXQ][2];
-#pragma unroll
-    for (int li = 0; li < 2; ++li) x1[li] = r1[li * nwm + w];
-#pragma unroll
-    for (int q = 0; q < TO_MAXQ; ++q) {
-      const uint64_t* r0 = LM + ((int64_t)(t - (q < nq ? ks.K[q] : 0)) * B + b) * 2 * nwm;
-#pragma unroll
-      for (int li = 0; li < 2; ++li) x0[q][li] = q < nq ? r0[li * nwm + w] : 0ull;
-    }
-#pragma unroll
-    for (int li = 0; li < 2; ++li) {
-      n1[li] += __popcll(x1[li]);
-#pragma unroll
-      for (int q = 0; q < TO_MAXQ; ++q) {
-        n0[q][li] += __popcll(x0[q][li]);
-        nb[q][li] += __popcll(x1[li] & x0[q][li]);
-      }
-    }
-  }
-  auto wsum = [](uint32_t v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-  };
-#pragma unroll
-  for (int li = 0; li < 2; ++li) {
-    n1[li] = wsum(n1[li]);
-#pragma unroll
-    for (int q = 0; q < TO_MAXQ; ++q) { n0[q][li] = wsum(n0[q][li]); nb[q][li] = wsum(nb[q][li]); }
-  }
-  if (lane < nq) {
-    const int q = lane;
-    const double* tp = TPv + (int64_t)tb * TP_STRIDE;
-    double x = 0.0;   // (k_turnover: the waves' f64 charge sums, +0.0 on an all-full row)
-#pragma unroll
-    for (int li = 0; li < 2; ++li) {
-      uint32_t c0 = 0, cb = 0;
-#pragma unroll
-      for (int qq = 0; qq < TO_MAXQ; ++qq)
-        if (qq == q) { c0 = n0[qq][li]; cb = nb[qq][li]; }
-      const double i1 = tp[li * (TO_MAXQ + 1)];
-      const double i0 = tp[li * (TO_MAXQ + 1) + 1 + q];
-      const double skq = tp[2 * (TO_MAXQ + 1) + 2 * q + li];
-      x += ((double)(n1[li] - cb) * i1 + (double)(c0 - cb) * i0 + (double)cb * fabs(i1 - i0)) * skq;
-    }
-    TURNp[((int64_t)q * rows + tb) * Ct + c] = 0.5 * x;
-    COSTp[((int64_t)q * rows + tb) * Ct + c] = x * half_spread;
-  }
-#endif
 }
 
 // Steady value-weight rows of the G = B / Bg panels that share one weight row (the grouped
@@ -1778,11 +1639,7 @@ __global__ __launch_bounds__(PF_THREADS) __attribute__((amdgpu_waves_per_eu(VWG_
           if (IMP) {   // turnover_body's charge, term for term
             double unit = half_spread;
             if (sra >= 0.0) {
-#ifdef VWG_NOSQRT   // A/B timing only (wrong costs): the charge without its square root
-              const double im = k_impact * unit_sig * (dw * sra);
-#else
               const double im = k_impact * unit_sig * (sqrt(dw) * sra);
-#endif
               unit = unit + ((im == im) ? im : 0.0);
             }
             cost[g][q] += dw * unit;
@@ -2138,7 +1995,7 @@ static int g_tune_cohort_lds = 1;
 // 1: label-sorted segment gathers (k_label_sort + k_cohort_seg) where N <= SEG_MAXN
 static int g_tune_cohort_seg = 1;
 // workgroups of the persistent general-row turnover launch (walking the work list)
-static int64_t g_tune_turn_gen_grid = 8192;   // C5 portfolio: 512 49.1, 2048 40.1, 8192 39.5 ms
+static int g_tune_turn_gen_grid = 8192;   // C5 portfolio: 512 49.1, 2048 40.1, 8192 39.5 ms
 // 1: k_overlap_rows (one thread per (t, b, decile) serving every K of the set) for single-chunk
 // cohort plans, 0: k_overlap always
 static int g_tune_overlap_rows = 1;
@@ -2171,14 +2028,16 @@ static void fill_i32(hipStream_t st, int32_t* p, int64_t n, int32_t v) {
 }
 
 struct PfPlan {
-  int C, kpar, Ct;
+  int C, Ct;
   int64_t CH, CHt;
 };
 
 // Enough workgroups to fill 256 CUs several times over, chunks of >= PF_CHUNK_MIN assets.
+// One workgroup walks its K cohorts over a chunk: cohort-parallel grids (a workgroup per cohort)
+// made tens of thousands of tiny workgroups at C3 and ran slower.
 // turnover workgroups wanted per launch (the row split into chunks to reach it); A/B knob
 // "turn_want" -- set it before the portfolio workspace is sized
-static int64_t g_tune_turn_want = 4096;
+static int g_tune_turn_want = 4096;
 static PfPlan pf_plan(int32_t T_m, int32_t B, int64_t N, int32_t K, int32_t n_bins) {
   PfPlan p;
   // Batches of up to PF_PLAN_MIN_B panels are planned as PF_PLAN_MIN_B panels: the sweeps join
@@ -2186,17 +2045,13 @@ static PfPlan pf_plan(int32_t T_m, int32_t B, int64_t N, int32_t K, int32_t n_bi
   // rank runs fewer of them (B = 1, 2), so a panel's turnover chunks -- and with them the bits
   // of its TURN / COST sums -- do not depend on how many look-backs share its launch.
   const int64_t rows = (int64_t)T_m * (B < PF_PLAN_MIN_B ? PF_PLAN_MIN_B : B);
-  const int64_t want = 4096;
+  const int64_t want = 4096;   // cohort workgroups wanted per launch (fixed; the turnover's is the knob)
   const int64_t cmax = (N + PF_CHUNK_MIN - 1) / PF_CHUNK_MIN;
   // the turnover chunking depends on (rows, N) only; the cohort chunk count also on whether the
   // segment path takes this (N, Kmax, n_bins) -- the same for every K of a portfolio_multi call,
   // so a cohort pass gives the same partial sums as the per-K calls (bit for bit).  The plan
   // reads the "cohort_seg" and "turn_want" tune knobs: set them BEFORE sizing a workspace
   // (csm_portfolio_workspace), never between sizing and the call
-  // (cohort-parallel grids, kpar = 1, made tens of thousands of tiny workgroups at C3 and
-  // ran slower than one workgroup walking its K cohorts over a chunk.)
-  (void)K;
-  p.kpar = 0;
   int64_t C = (want + rows - 1) / rows;
   C = C < 1 ? 1 : (C > cmax ? cmax : C);
   // the label-sorted segment path (launch_cohort) owns every segment whole in one of its first
@@ -2236,8 +2091,8 @@ static bool launch_cohort(hipStream_t st, const PfPlan& pl, const int8_t* L, con
                           const double* W, int T_m, int B, int64_t N, int K, double* SWRp,
                           double* SWp, double* FWp, char* segws, int64_t perm_b, int64_t off_b,
                           int64_t wsrt_b, bool legs, const PanAddr& pa, int64_t lm_b = 0) {
-  const dim3 g((unsigned)(pl.C * T_m * B), 1u, pl.kpar ? (unsigned)K : 1u);
-  if (g_tune_cohort_seg && segws && !pl.kpar && K * (NB + 1) <= SEG_MAXKD) {
+  const dim3 g((unsigned)(pl.C * T_m * B));
+  if (g_tune_cohort_seg && segws && K * (NB + 1) <= SEG_MAXKD) {
     uint16_t* PERM = (uint16_t*)(segws + perm_b);
     int32_t* OFF = (int32_t*)(segws + off_b);
     double* WSRT = (double*)(segws + wsrt_b);
@@ -2281,7 +2136,7 @@ static bool launch_cohort(hipStream_t st, const PfPlan& pl, const int8_t* L, con
     }
     return legs;
   }
-  if (g_tune_cohort_lds && !pl.kpar && K * NB <= AC_MAXKD) {
+  if (g_tune_cohort_lds && K * NB <= AC_MAXKD) {
     const dim3 g2((unsigned)(pl.C * T_m * B));
     if (W)
       hipLaunchKernelGGL((k_cohort_lds<NB, true>), g2, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B,
@@ -2293,10 +2148,10 @@ static bool launch_cohort(hipStream_t st, const PfPlan& pl, const int8_t* L, con
   }
   if (W)
     hipLaunchKernelGGL((k_cohort<NB, true>), g, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B, N, K,
-                       pl.C, pl.CH, pl.kpar, SWRp, SWp, FWp, pa);
+                       pl.C, pl.CH, SWRp, SWp, FWp, pa);
   else
     hipLaunchKernelGGL((k_cohort<NB, false>), g, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B, N, K,
-                       pl.C, pl.CH, pl.kpar, SWRp, SWp, FWp, pa);
+                       pl.C, pl.CH, SWRp, SWp, FWp, pa);
   return false;
 }
 
@@ -2407,47 +2262,22 @@ static PfLayout pf_layout(int32_t T_m, int32_t B, int64_t N, int32_t n_bins, int
   return l;
 }
 
+// this file's knobs (csm_tune forwards every key that is not in its own table)
+static const TuneKnob g_knobs[] = {
+    {"cohort_lds", &g_tune_cohort_lds, [](int v) { return v == 0 || v == 1; }},
+    {"cohort_seg", &g_tune_cohort_seg, [](int v) { return v == 0 || v == 1; }},
+    {"turn_want", &g_tune_turn_want, [](int v) { return v >= 1; }},
+    {"turn_gen_grid", &g_tune_turn_gen_grid, [](int v) { return v >= 1; }},
+    {"overlap_rows", &g_tune_overlap_rows, [](int v) { return v == 0 || v == 1; }},
+    {"gen_reset", &g_tune_gen_reset, [](int v) { return v == 0 || v == 1; }},
+    {"turn_vwg", &g_tune_turn_vwg, [](int v) { return v == 0 || v == 1; }},
+    {"turn_mask", &g_tune_turn_mask, [](int v) { return v == 0 || v == 1; }},
+    {"ls_opt", &g_tune_ls_opt, [](int v) { return v == 0 || v == 1; }},
+};
+
 extern "C" {
 
-int csm_tune_portfolio(const char* key, int value) {
-  if (key && !strcmp(key, "cohort_lds") && (value == 0 || value == 1)) {
-    g_tune_cohort_lds = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "cohort_seg") && (value == 0 || value == 1)) {
-    g_tune_cohort_seg = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "turn_want") && value >= 1) {
-    g_tune_turn_want = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "turn_gen_grid") && value >= 1) {
-    g_tune_turn_gen_grid = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "overlap_rows") && (value == 0 || value == 1)) {
-    g_tune_overlap_rows = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "gen_reset") && (value == 0 || value == 1)) {
-    g_tune_gen_reset = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "turn_vwg") && (value == 0 || value == 1)) {
-    g_tune_turn_vwg = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "turn_mask") && (value == 0 || value == 1)) {
-    g_tune_turn_mask = value;
-    return CSM_OK;
-  }
-  if (key && !strcmp(key, "ls_opt") && (value == 0 || value == 1)) {
-    g_tune_ls_opt = value;
-    return CSM_OK;
-  }
-  return CSM_E_INVAL;
-}
+int csm_tune_portfolio(const char* key, int value) { return tune_set(g_knobs, key, value); }
 
 int csm_tune_ptr_portfolio(const char* key, void* p) {
   if (key && !strcmp(key, "gen_probe")) {
@@ -2521,7 +2351,7 @@ int csm_cohort_sums_js(csm_ctx* ctx, int32_t nJ, const int8_t* const* L, const d
   const PfLayout lay = pf_layout(T_m, B, N, n_bins, Kmax);
   // one staged return row for every J: the segment path with one chunk per row; otherwise the
   // per-J passes (the same partials)
-  const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 && !lay.p.kpar &&
+  const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 &&
                       (legs ? nJ * Kmax * 4 : nJ * Kmax * (n_bins + 1)) <= SEG_MAXKD &&
                       (n_bins == 2 || n_bins == 3 || n_bins == 4 || n_bins == 5 || n_bins == 10 ||
                        n_bins == 20 || n_bins == 30);
@@ -2563,7 +2393,7 @@ int csm_cohort_sums_js_grouped(csm_ctx* ctx, int32_t nJ, const int8_t* L, const 
                    "(N=%lld)", SEG_MAXN, (long long)N);
   if (T_m == 0) return CSM_OK;
   const PfLayout lay = pf_layout(T_m, nJ * B, N, n_bins, Kmax);
-  const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 && !lay.p.kpar &&
+  const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 &&
                       (legs ? nJ * Kmax * 4 : nJ * Kmax * (n_bins + 1)) <= SEG_MAXKD &&
                       (n_bins == 2 || n_bins == 3 || n_bins == 4 || n_bins == 5 || n_bins == 10 ||
                        n_bins == 20 || n_bins == 30);
@@ -2603,7 +2433,7 @@ int csm_cohort_sums_legs(csm_ctx* ctx, const int8_t* L, const double* NR, const 
 // the leg bitplanes.  (Tune knobs are set before a workspace is sized, csmom.h.)
 static bool legs_masks(const PfLayout& lay, bool legs, int64_t N, int Kmax, int n_bins) {
   return g_tune_turn_mask && legs && (N & 3) == 0 && lay.seg && g_tune_cohort_seg &&
-         !lay.p.kpar && (int64_t)Kmax * (n_bins + 1) <= SEG_MAXKD &&
+         (int64_t)Kmax * (n_bins + 1) <= SEG_MAXKD &&
          (lay.p.Ct == 1 || lay.p.CHt % 256 == 0);
 }
 
@@ -2672,14 +2502,12 @@ static int portfolio_from_cohorts(csm_ctx* ctx, const int8_t* L, const double* W
       const unsigned gen_grid = (unsigned)std::min<int64_t>(nblk, g_tune_turn_gen_grid);
       // steady rows take their factors from k_turn_prep (no per-workgroup prologue: equal
       // weights since round 2, value weights / impact costs since round 4)
-      const bool prep = true;
-      double* TPv = prep ? (double*)((char*)workspace + lay.tp_b) : nullptr;
-      uint32_t* TPm = prep ? (uint32_t*)((char*)workspace + lay.tpm_b) : nullptr;
-      if (prep)
-        hipLaunchKernelGGL(k_turn_prep, dim3((unsigned)((lay.rows + TP_THREADS - 1) / TP_THREADS)),
-                           dim3(TP_THREADS), 0, st, (const double*)(ws + lay.fwt), T_m, B, ks, TPv,
-                           TPm, g_tune_gen_reset ? gen_count : (int32_t*)nullptr, lay.p.Ct,
-                           ws + lay.turn, ws + lay.cost);
+      double* TPv = (double*)((char*)workspace + lay.tp_b);
+      uint32_t* TPm = (uint32_t*)((char*)workspace + lay.tpm_b);
+      hipLaunchKernelGGL(k_turn_prep, dim3((unsigned)((lay.rows + TP_THREADS - 1) / TP_THREADS)),
+                         dim3(TP_THREADS), 0, st, (const double*)(ws + lay.fwt), T_m, B, ks, TPv,
+                         TPm, g_tune_gen_reset ? gen_count : (int32_t*)nullptr, lay.p.Ct,
+                         ws + lay.turn, ws + lay.cost);
       for (int gen = 0; gen < 2; ++gen) {
         int kq = 0;
         for (int q = 0; q < ks.n; ++q) kq = ks.K[q] > kq ? ks.K[q] : kq;
