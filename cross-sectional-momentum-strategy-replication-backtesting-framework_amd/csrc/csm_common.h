@@ -9,6 +9,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/csmom.h"
 
 #define ABSENT_BITS 0x7FF4000000000001ULL
@@ -29,8 +31,8 @@ struct csm_ctx {
   void* scratch;          // context-owned device workspace (k_deciles bucket ids), grown lazily
   size_t scratch_bytes;
   int n_cu;               // compute units of the device (decile kernel choice)
-  int32_t* dec_flg;       // [dec_flg_n] rows the merged decile pass left to the general kernel
-  int32_t dec_flg_n;      // (allocated at create, so a captured pipeline never allocates)
+  int32_t* dec_flg;       // one int per row the merged decile pass left to the general kernel
+  size_t dec_flg_bytes;   // (allocated at create, so a captured pipeline never allocates)
   int32_t* ticket;        // the fused long-short's arrival counter (zeroed at create; it wraps
                           // back to 0 on each decile launch's last increment)
   void* dsplit;           // the split decile pass's workspace (DecSplit), grown lazily
@@ -102,6 +104,22 @@ static inline int tune_set(const TuneKnob (&tab)[n], const char* key, int value)
 static inline bool capturing(csm_ctx* c) {
   hipStreamCaptureStatus s = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(c->stream, &s) == hipSuccess && s != hipStreamCaptureStatusNone;
+}
+// Grows the context-owned buffer *ptr (*have bytes) to at least `need` bytes; its contents are
+// not kept.
+template <typename T>
+static inline int ctx_reserve(csm_ctx* c, const char* who, const char* what, T** ptr,
+                              size_t* have, size_t need) {
+  if (*have >= need) return CSM_OK;
+  if (capturing(c))   // a captured graph would keep the freed buffer's address
+    return set_err(c, CSM_E_INVAL, "%s: %s (%zu B) must grow to %zu B during stream capture; "
+                   "run the call once before capturing", who, what, *have, need);
+  if (*ptr) HIP_CHECK(c, hipFree(*ptr));
+  *ptr = nullptr;
+  *have = 0;
+  HIP_CHECK(c, hipMalloc(ptr, need));
+  *have = need;
+  return CSM_OK;
 }
 
 // Device counters / flags the library resets before a launch that accumulates into them are
@@ -186,35 +204,66 @@ struct DecSplit {
   int pf;            // the sweep's prefetching variant (no more (chunk, date) pairs than CUs)
 };
 
-// narrow-row decile launcher (deciles_narrow.hip), NB in {0,2,3,4,5,10,20}
-template <int NB>
-void launch_deciles_narrow(bool v2, int T_m, hipStream_t st, const double* M, const double* NR,
-                           int64_t N, int nbins, const QTab& q, int8_t* L, double* EW,
-                           int32_t* CNT, int32_t* NV, int64_t* tim);
 
-// fused-pipeline decile launcher on the bucket ids of csm_signal_ids (deciles_pre.hip),
-// NB in {0,2,3,4,5,10,20}.  flg (T_m ints) non-NULL: the merged kernel first, then the general
-// kernel for the rows it left (flg[t] = 1); NULL: the general kernel only.  LS non-NULL (NB > 0,
-// with the context's ticket): the long-short by the general launch's last workgroup
-template <int NB>
-void launch_deciles_pre(int T_m, hipStream_t st, const double* M, const double* NR, int64_t N,
-                        int nbins, const QTab& q, int8_t* L, double* EW, int32_t* CNT,
-                        int32_t* NV, int64_t* tim, uint16_t* ids, int32_t* flg, double* LS,
-                        int32_t* ticket, int64_t cells);
+// Calls f(std::integral_constant<int, NB>{}) for the NB of the list that equals n_bins (the
+// kernels take the bin count as a template parameter); false, and no call, when none does.
+template <int... NBs, typename F>
+static inline bool nb_dispatch(int n_bins, F&& f) {
+  return ((n_bins == NBs && (f(std::integral_constant<int, NBs>{}), true)) || ...);
+}
 
+// The arguments of one decile pass, filled once by csmom.hip's deciles_dispatch and unpacked
+// into k_deciles's parameters at each launch (dec_launch).  A field the pass does not use is NULL.
+struct DecLaunch {
+  int T_m;            // date rows: one workgroup each
+  hipStream_t st;
+  const double* M;
+  const double* NR;   // NULL: labels only (NB = 0)
+  int64_t N;
+  int n_bins;
+  QTab q;
+  int8_t* L;
+  double* EW;
+  int32_t* CNT;
+  int32_t* NV;
+  int64_t* tim;
+  uint16_t* ids;      // the fixed map's bucket ids (the PRE kernels); NULL: the kernels that read M
+  int32_t* flg;       // [T_m] ints: the merged pass first, then the general kernel for the rows it
+                      // left (flg[t] = 1); NULL: the general kernel only
+  double* LS;         // with ticket (NB > 0): the long-short by the pass's last workgroup
+  int32_t* ticket;
+  bool v2;            // paired loads (the kernels that read M: even N, aligned M / NR / L)
+};
+
+// every k_deciles instantiation of deciles.inc; NB in {0, 2, 3, 4, 5, 10, 20}, 0 without NR
+using DecKernel = void (*)(const double*, const double*, int64_t, int, QTab, int8_t*, double*,
+                           int32_t*, int32_t*, int64_t*, uint16_t*, int32_t*, double*, int32_t*,
+                           DecSplit);
+template <typename F>
+static inline bool dec_nb_dispatch(const DecLaunch& a, F&& f) {
+  return nb_dispatch<0, 2, 3, 4, 5, 10, 20>(a.NR ? a.n_bins : 0, f);
+}
+// one workgroup of `threads` per row; flg / LS / ticket are the launch's own (a pass of several
+// launches gives them to some and NULL to others)
+static inline void dec_launch(DecKernel k, unsigned threads, const DecLaunch& a, int32_t* flg,
+                              double* LS, int32_t* ticket, DecSplit sp = DecSplit{}) {
+  void* args[] = {(void*)&a.M,  (void*)&a.NR,  (void*)&a.N,   (void*)&a.n_bins, (void*)&a.q,
+                  (void*)&a.L,  (void*)&a.EW,  (void*)&a.CNT, (void*)&a.NV,     (void*)&a.tim,
+                  (void*)&a.ids, &flg,         &LS,           &ticket,          &sp};
+  (void)hipLaunchKernel((const void*)k, dim3(a.T_m), dim3(threads), args, 0, a.st);
+}
+
+// The decile launchers; each returns false, having launched nothing, when n_bins is not a
+// compiled NB (dec_nb_dispatch).
+// rows of a few thousand assets reading M (deciles_narrow.hip)
+bool launch_deciles_narrow(const DecLaunch& a);
+// the fused pipeline's wide rows on ids (deciles_pre.hip); the merged pass sums in the split
+// pass's order, its chunks of `cells` cells
+bool launch_deciles_pre(const DecLaunch& a, int64_t cells);
 // the split pass (plan, chunked sweep, finish + the general path for the rows it leaves) on
-// wide rows of short date shards; flg (T_m ints) required
-template <int NB>
-void launch_deciles_split(int T_m, hipStream_t st, const double* M, const double* NR, int64_t N,
-                          int nbins, const QTab& q, int8_t* L, double* EW, int32_t* CNT,
-                          int32_t* NV, int64_t* tim, uint16_t* ids, int32_t* flg,
-                          const DecSplit& sp, double* LS, int32_t* ticket);
-
-// the same on narrow rows (deciles_npre.hip: 2048 buckets = the fixed map's ids >> 2); flg
-// non-NULL with decile sums: ONE launch, a row the merged pass gives up taking the general path
-// in the same workgroup
-template <int NB>
-void launch_deciles_pre_narrow(int T_m, hipStream_t st, const double* M, const double* NR,
-                               int64_t N, int nbins, const QTab& q, int8_t* L, double* EW,
-                               int32_t* CNT, int32_t* NV, int64_t* tim, uint16_t* ids,
-                               int32_t* flg, double* LS, int32_t* ticket);
+// wide rows of short date shards; a.flg required
+bool launch_deciles_split(const DecLaunch& a, const DecSplit& sp);
+// narrow rows on ids (deciles_npre.hip: 2048 buckets = the fixed map's ids >> 2); a.flg with
+// decile sums: ONE launch, a row the merged pass gives up taking the general path in the same
+// workgroup
+bool launch_deciles_pre_narrow(const DecLaunch& a);

@@ -2591,8 +2591,8 @@ int csm_create(int device, csm_ctx** out) {
   c->stream = nullptr;
   if (hipDeviceGetAttribute(&c->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess)
     c->n_cu = 256;
-  c->dec_flg_n = 1 << 16;
-  if (hipMalloc(&c->dec_flg, (size_t)c->dec_flg_n * sizeof(int32_t)) != hipSuccess) {
+  c->dec_flg_bytes = ((size_t)1 << 16) * sizeof(int32_t);
+  if (hipMalloc(&c->dec_flg, c->dec_flg_bytes) != hipSuccess) {
     free(c);
     return CSM_E_HIP;
   }
@@ -2877,77 +2877,6 @@ int csm_signal_shard_ids(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
 
 }  // extern "C"
 
-template <int NB>
-static void launch_deciles(bool v2, int T_m, hipStream_t st, const double* M, const double* NR,
-                           int64_t N, int nbins, const QTab& q, int8_t* L, double* EW,
-                           int32_t* CNT, int32_t* NV, uint16_t* ids, bool pre = false,
-                           int32_t* flg = nullptr, double* LS = nullptr,
-                           int32_t* ticket = nullptr) {
-  int64_t* tm = g_dec_timing;
-  if (pre) {   // ids written by csm_signal_ids / csm_momentum_multi_ids (fixed map): M is read only for a few cells
-    if (N <= g_tune_dec_narrow_max)   // sweep rows: 2048 buckets (the fixed map's ids >> 2)
-      launch_deciles_pre_narrow<NB>(T_m, st, M, NR, N, nbins, q, L, EW, CNT, NV, tm, ids,
-                                    g_tune_dec_merge ? flg : nullptr, LS, ticket);
-    else
-      launch_deciles_pre<NB>(T_m, st, M, NR, N, nbins, q, L, EW, CNT, NV, tm, ids,
-                             g_tune_dec_merge ? flg : nullptr, LS, ticket, g_tune_dec_split_cells);
-    return;
-  }
-  if (N <= g_tune_dec_narrow_max) {   // rows of a few thousand assets (C2/C3/C5)
-    launch_deciles_narrow<NB>(v2, T_m, st, M, NR, N, nbins, q, L, EW, CNT, NV, tm);
-    return;
-  }
-  if (v2) hipLaunchKernelGGL((k_deciles<NB, true>), dim3(T_m), dim3(dec_wide::kThreads), 0, st, M, NR, N, nbins, q, L, EW, CNT, NV, tm, ids);
-  else hipLaunchKernelGGL((k_deciles<NB, false>), dim3(T_m), dim3(dec_wide::kThreads), 0, st, M, NR, N, nbins, q, L, EW, CNT, NV, tm, ids);
-}
-
-extern "C" {
-
-int csm_deciles(csm_ctx* ctx, const double* M, const double* NR, int32_t T_m, int64_t N,
-                int32_t n_bins, const double* qtable, int8_t* L, double* EW, int32_t* CNT,
-                int32_t* NV) {
-  int r = prep(ctx);
-  if (r) return r;
-  if (!M || !L || !qtable || N <= 0 || T_m < 0 || n_bins < 1 || n_bins > MAXQ - 1 || N > 0x7FFFFFFFLL)
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles: bad arguments (N=%lld T_m=%d n_bins=%d)",
-                   (long long)N, T_m, n_bins);
-  if (NR && (!EW || !CNT))
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles: EW and CNT are required when NR is given");
-  if (T_m == 0) return CSM_OK;
-  QTab q;
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
-  const bool v2 = (N % 2 == 0) && aligned16(M) && (!NR || aligned16(NR)) && (((uintptr_t)L & 1u) == 0);
-  uint16_t* ids = nullptr;
-  if (!NR) {
-    launch_deciles<0>(v2, T_m, ctx->stream, M, nullptr, N, n_bins, q, L, nullptr, nullptr, NV, ids);
-  } else {
-    switch (n_bins) {
-      case 2: launch_deciles<2>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids); break;
-      case 3: launch_deciles<3>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids); break;
-      case 4: launch_deciles<4>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids); break;
-      case 5: launch_deciles<5>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids); break;
-      case 10: launch_deciles<10>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids); break;
-      case 20: launch_deciles<20>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids); break;
-      default:
-        return set_err(ctx, CSM_E_INVAL, "csm_deciles: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", n_bins);
-    }
-  }
-  LAUNCH_CHECK(ctx, "k_deciles");
-  return CSM_OK;
-}
-
-int csm_long_short(csm_ctx* ctx, const double* EW, const int32_t* CNT, int32_t T_m,
-                   int32_t n_bins, double* LS) {
-  int r = prep(ctx);
-  if (r) return r;
-  if (!EW || !CNT || !LS || T_m < 0 || n_bins < 1)
-    return set_err(ctx, CSM_E_INVAL, "csm_long_short: bad arguments");
-  if (T_m == 0) return CSM_OK;
-  hipLaunchKernelGGL(k_long_short, dim3(1), dim3(LS_THREADS), 0, ctx->stream, EW, CNT, T_m, n_bins, LS);
-  LAUNCH_CHECK(ctx, "k_long_short");
-  return CSM_OK;
-}
-
 // The split decile pass's workspace for T_m rows of N cells (csm_common.h DecSplit), carved
 // from one context buffer; sized for n_bins up to MAXQ so one buffer serves every NB.
 static size_t dsplit_layout(int32_t T_m, int64_t N, DecSplit* sp, char* base) {
@@ -2974,150 +2903,158 @@ static size_t dsplit_layout(int32_t T_m, int64_t N, DecSplit* sp, char* base) {
   return o;
 }
 
-static int deciles_dispatch(csm_ctx* ctx, const char* who, bool v2, int32_t T_m,
-                            const double* M, const double* NR, int64_t N, int32_t n_bins,
-                            const QTab& q, int8_t* L, double* EW, int32_t* CNT, int32_t* NV,
-                            uint16_t* ids, bool pre, double* LS = nullptr) {
-  // LS (the ids path only): narrow rows form the long-short in the decile launch (its last
-  // workgroup); wide rows (C4) with k_long_short after it -- measured the same there
-  // (1.968 vs 1.971 ms/step), and the general kernel stays free of the per-workgroup fence
-  double* LSw = (LS && N > g_tune_dec_narrow_max) ? LS : nullptr;
-  if (LSw) LS = nullptr;
-  int32_t* tk = LS ? ctx->ticket : nullptr;
-  int32_t* flg = nullptr;
-  if (pre) {
-    if (ctx->dec_flg_n < T_m) {   // beyond the create-time capacity
-      if (capturing(ctx))           // a captured graph would keep the freed buffer's address
-        return set_err(ctx, CSM_E_INVAL, "%s: %d rows exceed the context's row-flag buffer (%d) "
-                       "during stream capture; run the call once before capturing", who, T_m,
-                       ctx->dec_flg_n);
-      if (ctx->dec_flg) HIP_CHECK(ctx, hipFree(ctx->dec_flg));
-      ctx->dec_flg = nullptr;
-      ctx->dec_flg_n = 0;
-      HIP_CHECK(ctx, hipMalloc(&ctx->dec_flg, (size_t)T_m * sizeof(int32_t)));
-      ctx->dec_flg_n = T_m;
-    }
-    flg = ctx->dec_flg;
+// What every decile entry point does first: prep, the checks they share, and the launch
+// arguments with the quantile table filled in.  The caller adds its own checks, returns CSM_OK
+// for T_m == 0 and hands *a to deciles_dispatch.
+static int dec_args(csm_ctx* ctx, const char* who, const double* M, const double* NR,
+                    const uint16_t* ids, int32_t T_m, int64_t N, int32_t n_bins,
+                    const double* qtable, int8_t* L, double* EW, int32_t* CNT, int32_t* NV,
+                    double* LS, DecLaunch* a) {
+  int r = prep(ctx);
+  if (r) return r;
+  if (!M || !L || !qtable || N <= 0 || T_m < 0 || n_bins < 1 || n_bins > MAXQ - 1 || N > 0x7FFFFFFFLL)
+    return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (N=%lld T_m=%d n_bins=%d)", who,
+                   (long long)N, T_m, n_bins);
+  const bool v2 = (N % 2 == 0) && aligned16(M) && (!NR || aligned16(NR)) && (((uintptr_t)L & 1u) == 0);
+  *a = DecLaunch{T_m, ctx->stream, M, NR, N, n_bins, QTab{}, L, NR ? EW : nullptr,
+                 NR ? CNT : nullptr, NV, g_dec_timing, const_cast<uint16_t*>(ids), nullptr, LS,
+                 nullptr, v2};
+  for (int i = 0; i < MAXQ; ++i) a->q.q[i] = i <= n_bins ? qtable[i] : 1.0;
+  return CSM_OK;
+}
+
+// One decile pass: picks the kernels for the row width, the ids (a.ids: the PRE kernels) and the
+// tune knobs, and fills in a.flg and a.ticket.  a.LS: narrow rows on ids form the long-short in
+// the decile launch (its last workgroup), and so does the split pass; every other pass with
+// k_long_short after it -- measured the same on C4's wide rows (1.968 vs 1.971 ms/step), and
+// the general kernel stays free of the per-workgroup fence
+static int deciles_dispatch(csm_ctx* ctx, const char* who, DecLaunch a) {
+  const bool pre = a.ids != nullptr, wide = a.N > g_tune_dec_narrow_max;
+  double* LSw = (wide || !pre) ? a.LS : nullptr;
+  if (LSw) a.LS = nullptr;
+  bool ok;
+  if (pre) {   // ids written by csm_signal_ids / csm_momentum_multi_ids: M is read only for a few cells
+    int r = ctx_reserve(ctx, who, "the context's row-flag buffer", &ctx->dec_flg,
+                        &ctx->dec_flg_bytes, (size_t)a.T_m * sizeof(int32_t));
+    if (r) return r;
+    a.flg = g_tune_dec_merge ? ctx->dec_flg : nullptr;
     // wide rows of a short date shard (fewer rows than half the CUs: one workgroup per row
     // leaves most of the chip idle): the split pass (plan, chunked sweep over the whole chip,
     // finish with the fused long-short) when the row's (chunk, wave) lists fit the finish
     // launch's merge.  Same labels and counts as the merged pass; means in another fixed order.
-    const int64_t C = (N + g_tune_dec_split_cells - 1) / g_tune_dec_split_cells;
+    const int64_t C = (a.N + g_tune_dec_split_cells - 1) / g_tune_dec_split_cells;
     const bool split = g_tune_dec_split == 1 ||
-                       (g_tune_dec_split == 2 && (int64_t)T_m * 2 <= (int64_t)ctx->n_cu);
-    if (split && g_tune_dec_merge && !q.legs && N > g_tune_dec_narrow_max &&
-        C * SPLIT_WAVES <= DSPLIT_MAXL) {
-      const size_t need = dsplit_layout(T_m, N, nullptr, nullptr);
-      if (ctx->dsplit_bytes < need) {
-        if (capturing(ctx))
-          return set_err(ctx, CSM_E_INVAL, "%s: the split decile workspace (%zu B) must grow to %zu B "
-                         "during stream capture; run the call once before capturing", who,
-                         ctx->dsplit_bytes, need);
-        if (ctx->dsplit) HIP_CHECK(ctx, hipFree(ctx->dsplit));
-        ctx->dsplit = nullptr;
-        ctx->dsplit_bytes = 0;
-        HIP_CHECK(ctx, hipMalloc(&ctx->dsplit, need));
-        ctx->dsplit_bytes = need;
-      }
+                       (g_tune_dec_split == 2 && (int64_t)a.T_m * 2 <= (int64_t)ctx->n_cu);
+    if (split && a.flg && !a.q.legs && wide && C * SPLIT_WAVES <= DSPLIT_MAXL) {
+      r = ctx_reserve(ctx, who, "the split decile workspace", &ctx->dsplit, &ctx->dsplit_bytes,
+                      dsplit_layout(a.T_m, a.N, nullptr, nullptr));
+      if (r) return r;
       DecSplit sp;
-      dsplit_layout(T_m, N, &sp, (char*)ctx->dsplit);
-      sp.pf = g_tune_dec_split_pf == 2 ? (C * T_m <= (int64_t)ctx->n_cu) : g_tune_dec_split_pf;
-      int64_t* tm = g_dec_timing;
-      double* lsx = NR ? LSw : nullptr;
-      int32_t* tkx = lsx ? ctx->ticket : nullptr;
-      switch (NR ? n_bins : 0) {
-#define DS_CASE(NBV) case NBV: launch_deciles_split<NBV>(T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, tm, ids, flg, sp, lsx, tkx); break;
-        DS_CASE(0) DS_CASE(2) DS_CASE(3) DS_CASE(4) DS_CASE(5) DS_CASE(10) DS_CASE(20)
-#undef DS_CASE
-        default:
-          return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", who, n_bins);
-      }
-      LAUNCH_CHECK(ctx, who);
-      return CSM_OK;
+      dsplit_layout(a.T_m, a.N, &sp, (char*)ctx->dsplit);
+      sp.pf = g_tune_dec_split_pf == 2 ? (C * a.T_m <= (int64_t)ctx->n_cu) : g_tune_dec_split_pf;
+      a.LS = LSw;
+      LSw = nullptr;
+      a.ticket = a.LS ? ctx->ticket : nullptr;
+      ok = launch_deciles_split(a, sp);
+    } else {
+      a.ticket = a.LS ? ctx->ticket : nullptr;
+      // sweep rows: 2048 buckets (the fixed map's ids >> 2)
+      ok = wide ? launch_deciles_pre(a, g_tune_dec_split_cells) : launch_deciles_pre_narrow(a);
     }
-  }
-  if (!NR) {
-    launch_deciles<0>(v2, T_m, ctx->stream, M, nullptr, N, n_bins, q, L, nullptr, nullptr, NV, ids, pre, flg);
+  } else if (!wide) {   // rows of a few thousand assets (C2/C3/C5)
+    ok = launch_deciles_narrow(a);
   } else {
-    switch (n_bins) {
-      case 2: launch_deciles<2>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids, pre, flg, LS, tk); break;
-      case 3: launch_deciles<3>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids, pre, flg, LS, tk); break;
-      case 4: launch_deciles<4>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids, pre, flg, LS, tk); break;
-      case 5: launch_deciles<5>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids, pre, flg, LS, tk); break;
-      case 10: launch_deciles<10>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids, pre, flg, LS, tk); break;
-      case 20: launch_deciles<20>(v2, T_m, ctx->stream, M, NR, N, n_bins, q, L, EW, CNT, NV, ids, pre, flg, LS, tk); break;
-      default:
-        return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", who, n_bins);
-    }
+    ok = dec_nb_dispatch(a, [&](auto nb) {
+      constexpr int NB = decltype(nb)::value;
+      dec_launch(a.v2 ? k_deciles<NB, true> : k_deciles<NB, false>, dec_wide::kThreads, a, nullptr,
+                 nullptr, nullptr);
+    });
   }
+  if (!ok)
+    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", who,
+                   a.n_bins);
   LAUNCH_CHECK(ctx, who);
   if (LSw) {
-    hipLaunchKernelGGL(k_long_short, dim3(1), dim3(LS_THREADS), 0, ctx->stream, EW, CNT, T_m, n_bins, LSw);
+    hipLaunchKernelGGL(k_long_short, dim3(1), dim3(LS_THREADS), 0, ctx->stream, a.EW, a.CNT, a.T_m,
+                       a.n_bins, LSw);
     LAUNCH_CHECK(ctx, "k_long_short");
   }
   return CSM_OK;
 }
 
-static bool ids_ok(int64_t N, const double* M, const double* NR, const int8_t* L, const uint16_t* ids) {
-  return ids && (N % 4) == 0 && ((uintptr_t)ids & 7u) == 0 && aligned16(M) && (!NR || aligned16(NR)) &&
-         (((uintptr_t)L & 3u) == 0);
+// the ids entry points' own check (NR may be NULL)
+static int ids_check(csm_ctx* ctx, const char* who, const DecLaunch& a) {
+  if (a.ids && (a.N % 4) == 0 && ((uintptr_t)a.ids & 7u) == 0 && aligned16(a.M) &&
+      (!a.NR || aligned16(a.NR)) && (((uintptr_t)a.L & 3u) == 0))
+    return CSM_OK;
+  return set_err(ctx, CSM_E_INVAL, "%s: needs N %% 4 == 0, 8-B aligned ids, 16-B aligned M / NR, "
+                 "4-B aligned L (N=%lld)", who, (long long)a.N);
+}
+
+extern "C" {
+
+int csm_deciles(csm_ctx* ctx, const double* M, const double* NR, int32_t T_m, int64_t N,
+                int32_t n_bins, const double* qtable, int8_t* L, double* EW, int32_t* CNT,
+                int32_t* NV) {
+  DecLaunch a;
+  int r = dec_args(ctx, "csm_deciles", M, NR, nullptr, T_m, N, n_bins, qtable, L, EW, CNT, NV,
+                   nullptr, &a);
+  if (r) return r;
+  if (NR && (!EW || !CNT))
+    return set_err(ctx, CSM_E_INVAL, "csm_deciles: EW and CNT are required when NR is given");
+  if (T_m == 0) return CSM_OK;
+  return deciles_dispatch(ctx, "csm_deciles", a);
+}
+
+int csm_long_short(csm_ctx* ctx, const double* EW, const int32_t* CNT, int32_t T_m,
+                   int32_t n_bins, double* LS) {
+  int r = prep(ctx);
+  if (r) return r;
+  if (!EW || !CNT || !LS || T_m < 0 || n_bins < 1)
+    return set_err(ctx, CSM_E_INVAL, "csm_long_short: bad arguments");
+  if (T_m == 0) return CSM_OK;
+  hipLaunchKernelGGL(k_long_short, dim3(1), dim3(LS_THREADS), 0, ctx->stream, EW, CNT, T_m, n_bins, LS);
+  LAUNCH_CHECK(ctx, "k_long_short");
+  return CSM_OK;
 }
 
 int csm_deciles_ids(csm_ctx* ctx, const double* M, const double* NR, const uint16_t* ids,
                     int32_t T_m, int64_t N, int32_t n_bins, const double* qtable, int8_t* L,
                     double* EW, int32_t* CNT, int32_t* NV) {
-  int r = prep(ctx);
+  DecLaunch a;
+  int r = dec_args(ctx, "csm_deciles_ids", M, NR, ids, T_m, N, n_bins, qtable, L, EW, CNT, NV,
+                   nullptr, &a);
   if (r) return r;
-  if (!M || !L || !qtable || N <= 0 || T_m < 0 || n_bins < 1 || n_bins > MAXQ - 1 || N > 0x7FFFFFFFLL)
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids: bad arguments (N=%lld T_m=%d n_bins=%d)",
-                   (long long)N, T_m, n_bins);
   if (NR && (!EW || !CNT))
     return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids: EW and CNT are required when NR is given");
-  if (!ids_ok(N, M, NR, L, ids))
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids: needs N %% 4 == 0, 8-B aligned ids, 16-B aligned "
-                   "M / NR, 4-B aligned L (N=%lld)", (long long)N);
+  if ((r = ids_check(ctx, "csm_deciles_ids", a))) return r;
   if (T_m == 0) return CSM_OK;
-  QTab q;
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
-  return deciles_dispatch(ctx, "csm_deciles_ids", true, T_m, M, NR, N, n_bins, q, L, EW, CNT, NV,
-                          const_cast<uint16_t*>(ids), true);
+  return deciles_dispatch(ctx, "csm_deciles_ids", a);
 }
 
 int csm_deciles_ids_legs(csm_ctx* ctx, const double* M, const uint16_t* ids, int32_t T_m,
                          int64_t N, int32_t n_bins, const double* qtable, int8_t* L, int32_t* NV) {
-  int r = prep(ctx);
-  if (r) return r;
-  if (!M || !L || !qtable || N <= 0 || T_m < 0 || n_bins < 1 || n_bins > MAXQ - 1 || N > 0x7FFFFFFFLL)
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids_legs: bad arguments (N=%lld T_m=%d n_bins=%d)",
-                   (long long)N, T_m, n_bins);
-  if (!ids_ok(N, M, nullptr, L, ids))
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids_legs: needs N %% 4 == 0, 8-B aligned ids, "
-                   "16-B aligned M, 4-B aligned L (N=%lld)", (long long)N);
+  DecLaunch a;
+  int r = dec_args(ctx, "csm_deciles_ids_legs", M, nullptr, ids, T_m, N, n_bins, qtable, L,
+                   nullptr, nullptr, NV, nullptr, &a);
+  if (r || (r = ids_check(ctx, "csm_deciles_ids_legs", a))) return r;
   if (T_m == 0) return CSM_OK;
-  QTab q;
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
-  q.legs = 1;
-  return deciles_dispatch(ctx, "csm_deciles_ids_legs", true, T_m, M, nullptr, N, n_bins, q, L,
-                          nullptr, nullptr, NV, const_cast<uint16_t*>(ids), true);
+  a.q.legs = 1;
+  return deciles_dispatch(ctx, "csm_deciles_ids_legs", a);
 }
 
 int csm_deciles_ids_ls(csm_ctx* ctx, const double* M, const double* NR, const uint16_t* ids,
                        int32_t T_m, int64_t N, int32_t n_bins, const double* qtable, int8_t* L,
                        double* EW, int32_t* CNT, int32_t* NV, double* LS) {
-  int r = prep(ctx);
+  DecLaunch a;
+  int r = dec_args(ctx, "csm_deciles_ids_ls", M, NR, ids, T_m, N, n_bins, qtable, L, EW, CNT, NV,
+                   LS, &a);
   if (r) return r;
-  if (!M || !NR || !EW || !CNT || !LS || !L || !qtable || N <= 0 || T_m < 0 || n_bins < 1 ||
-      n_bins > MAXQ - 1 || N > 0x7FFFFFFFLL)
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids_ls: bad arguments (N=%lld T_m=%d n_bins=%d; "
-                   "NR, EW, CNT and LS required)", (long long)N, T_m, n_bins);
-  if (!ids_ok(N, M, NR, L, ids))
-    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids_ls: needs N %% 4 == 0, 8-B aligned ids, 16-B "
-                   "aligned M / NR, 4-B aligned L (N=%lld)", (long long)N);
+  if (!NR || !EW || !CNT || !LS)
+    return set_err(ctx, CSM_E_INVAL, "csm_deciles_ids_ls: NR, EW, CNT and LS are required");
+  if ((r = ids_check(ctx, "csm_deciles_ids_ls", a))) return r;
   if (T_m == 0) return CSM_OK;
-  QTab q;
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
-  return deciles_dispatch(ctx, "csm_deciles_ids_ls", true, T_m, M, NR, N, n_bins, q, L, EW, CNT,
-                          NV, const_cast<uint16_t*>(ids), true, LS);
+  return deciles_dispatch(ctx, "csm_deciles_ids_ls", a);
 }
 
 int csm_pipeline(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N, const int64_t* month_start,
@@ -3125,47 +3062,30 @@ int csm_pipeline(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N, const in
                  int32_t skip, int32_t n_bins,
                  const double* qtable, double* PM, double* R, double* M, double* NR, int8_t* L,
                  double* EW, int32_t* CNT, int32_t* NV, double* LS) {
-  int r = prep(ctx);
+  DecLaunch a;
+  int r = dec_args(ctx, "csm_pipeline", M, NR, nullptr, T_m, N, n_bins, qtable, L, EW, CNT, NV,
+                   LS, &a);
   if (r) return r;
-  if (!P || !month_start || !qtable || !M || !NR || !L || !EW || !CNT || !LS || N <= 0 ||
-      T_m < 0 || n_bins < 1 || n_bins > MAXQ - 1 || N > 0x7FFFFFFFLL)
+  if (!P || !month_start || !NR || !EW || !CNT || !LS)
     return set_err(ctx, CSM_E_INVAL, "csm_pipeline: bad arguments (N=%lld T_m=%d n_bins=%d)",
                    (long long)N, T_m, n_bins);
   if (T_m == 0) return CSM_OK;
   // the id path needs 4-aligned rows and the wide decile kernel; otherwise signal + deciles
-  uint16_t* ids = nullptr;
   const bool want_ids = (N % 4) == 0 && N > g_tune_dec_narrow_max && aligned16(P) && aligned16(M) &&
                         aligned16(NR) && (((uintptr_t)L & 3u) == 0) && (!PM || aligned16(PM)) &&
                         (!R || aligned16(R));
   if (want_ids) {
-    const size_t need = (size_t)T_m * (size_t)N * sizeof(uint16_t);
-    if (ctx->scratch_bytes < need) {
-      if (capturing(ctx))
-        return set_err(ctx, CSM_E_INVAL, "csm_pipeline: the bucket-id scratch (%zu B) must grow to "
-                       "%zu B during stream capture; run the call once before capturing",
-                       ctx->scratch_bytes, need);
-      if (ctx->scratch) HIP_CHECK(ctx, hipFree(ctx->scratch));
-      ctx->scratch = nullptr;
-      ctx->scratch_bytes = 0;
-      HIP_CHECK(ctx, hipMalloc(&ctx->scratch, need));
-      ctx->scratch_bytes = need;
-    }
-    ids = (uint16_t*)ctx->scratch;
+    r = ctx_reserve(ctx, "csm_pipeline", "the bucket-id scratch", &ctx->scratch,
+                    &ctx->scratch_bytes, (size_t)T_m * (size_t)N * sizeof(uint16_t));
+    if (r) return r;
+    a.ids = (uint16_t*)ctx->scratch;
   }
   (void)min_month_days;
   r = signal_launch(ctx, "csm_pipeline", P, T_d, N, month_start, T_m, max_month_days, J,
-                    skip, PM, R, M, NR, nullptr, nullptr, nullptr, false, ids);
+                    skip, PM, R, M, NR, nullptr, nullptr, nullptr, false, a.ids);
   if (r) return r;
-  QTab q;
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
-  const bool v2 = (N % 2 == 0) && aligned16(M) && aligned16(NR) && (((uintptr_t)L & 1u) == 0);
   // the id path: labels, decile means and the long-short in one launch
-  r = deciles_dispatch(ctx, "csm_pipeline", v2, T_m, M, NR, N, n_bins, q, L, EW, CNT, NV, ids,
-                       ids != nullptr, ids ? LS : nullptr);
-  if (r || ids) return r;
-  hipLaunchKernelGGL(k_long_short, dim3(1), dim3(LS_THREADS), 0, ctx->stream, EW, CNT, T_m, n_bins, LS);
-  LAUNCH_CHECK(ctx, "k_long_short");
-  return CSM_OK;
+  return deciles_dispatch(ctx, "csm_pipeline", a);
 }
 
 int csm_shard_summary(csm_ctx* ctx, const double* PM, int32_t T_m, int64_t N, int32_t J,
@@ -3591,18 +3511,10 @@ int csm_signal_chunked(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
                             : (const void*)k_signal_tc<0>;
   if (lds > 65536)
     HIP_CHECK(ctx, hipFuncSetAttribute(kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  if (W == 13 && J == 12)
-    hipLaunchKernelGGL((k_signal_tc<13, 12>), dim3((unsigned)(C * nbx)), dim3(TC_THREADS), lds,
-                       ctx->stream, P, month_start, T_m, N, J, skip, C, nbx, R, M, NR, ids, rec,
-                       sync, g_tune_tc_spins);
-  else if (W == 13)
-    hipLaunchKernelGGL(k_signal_tc<13>, dim3((unsigned)(C * nbx)), dim3(TC_THREADS), lds,
-                       ctx->stream, P, month_start, T_m, N, J, skip, C, nbx, R, M, NR, ids, rec,
-                       sync, g_tune_tc_spins);
-  else
-    hipLaunchKernelGGL(k_signal_tc<0>, dim3((unsigned)(C * nbx)), dim3(TC_THREADS), lds,
-                       ctx->stream, P, month_start, T_m, N, J, skip, C, nbx, R, M, NR, ids, rec,
-                       sync, g_tune_tc_spins);
+  void* args[] = {(void*)&P, (void*)&month_start, &T_m, &N, &J, &skip, &C, (void*)&nbx, &R, &M, &NR,
+                  &ids, &rec, &sync, &g_tune_tc_spins};
+  HIP_CHECK(ctx, hipLaunchKernel(kfn, dim3((unsigned)(C * nbx)), dim3(TC_THREADS), args, lds,
+                                 ctx->stream));
   LAUNCH_CHECK(ctx, "k_signal_tc");
   return CSM_OK;
 }

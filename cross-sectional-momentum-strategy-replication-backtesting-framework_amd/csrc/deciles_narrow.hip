@@ -13,28 +13,10 @@ namespace dec_narrow {
 #include "deciles.inc"
 }  // namespace dec_narrow
 
-template <int NB>
-void launch_deciles_narrow(bool v2, int T_m, hipStream_t st, const double* M, const double* NR,
-                           int64_t N, int nbins, const QTab& q, int8_t* L, double* EW,
-                           int32_t* CNT, int32_t* NV, int64_t* tim) {
-  uint16_t* ids = nullptr;
-  if (v2)
-    hipLaunchKernelGGL((dec_narrow::k_deciles<NB, true, false>), dim3(T_m), dim3(DEC_THREADS), 0,
-                       st, M, NR, N, nbins, q, L, EW, CNT, NV, tim, ids);
-  else
-    hipLaunchKernelGGL((dec_narrow::k_deciles<NB, false, false>), dim3(T_m), dim3(DEC_THREADS), 0,
-                       st, M, NR, N, nbins, q, L, EW, CNT, NV, tim, ids);
+bool launch_deciles_narrow(const DecLaunch& a) {
+  return dec_nb_dispatch(a, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    dec_launch(a.v2 ? dec_narrow::k_deciles<NB, true, false> : dec_narrow::k_deciles<NB, false, false>,
+               DEC_THREADS, a, nullptr, nullptr, nullptr);
+  });
 }
-
-#define INST(NB)                                                                              \
-  template void launch_deciles_narrow<NB>(bool, int, hipStream_t, const double*, const double*,  \
-                                          int64_t, int, const QTab&, int8_t*, double*,           \
-                                          int32_t*, int32_t*, int64_t*);
-INST(0)
-INST(2)
-INST(3)
-INST(4)
-INST(5)
-INST(10)
-INST(20)
-#undef INST

@@ -17,44 +17,23 @@ namespace dec_npre {
 
 // the fused sweep path on bucket ids (csm_momentum_multi_ids -> csm_deciles_ids on rows of
 // <= dec_narrow_max assets): merged pass, then the general PRE kernel for the rows it leaves
-template <int NB>
-void launch_deciles_pre_narrow(int T_m, hipStream_t st, const double* M, const double* NR,
-                               int64_t N, int nbins, const QTab& q, int8_t* L, double* EW,
-                               int32_t* CNT, int32_t* NV, int64_t* tim,
-                               uint16_t* ids, int32_t* flg, double* LS,
-                               int32_t* ticket) {
+bool launch_deciles_pre_narrow(const DecLaunch& a) {
   // with decile sums (C2): ONE launch -- a row the merged pass gives up takes the general path
   // in the same workgroup, and LS (with the context's ticket) is formed by the last workgroup.
   // Labels only (the sweeps, NB = 0): the merged kernel keeps its 8 workgroups per CU only
   // without the general path beside it (64 VGPRs; with it the kernel spills), so the general
   // kernel follows as its own launch for the rows the merged pass left (flg[t] = 1).
-  if constexpr (NB > 0) {
-    if (flg) {
-      hipLaunchKernelGGL((dec_npre::k_deciles<NB, true, true, true, true>), dim3(T_m),
-                         dim3(DEC_THREADS), 0, st, M, NR, N, nbins, q, L, EW, CNT, NV, tim,
-                         ids, (int32_t*)nullptr, LS, ticket);
-      return;
+  return dec_nb_dispatch(a, [&](auto nb) {
+    constexpr int NB = decltype(nb)::value;
+    if constexpr (NB > 0) {
+      if (a.flg) {
+        dec_launch(dec_npre::k_deciles<NB, true, true, true, true>, DEC_THREADS, a, nullptr, a.LS,
+                   a.ticket);
+        return;
+      }
     }
-  }
-  if (flg)
-    hipLaunchKernelGGL((dec_npre::k_deciles<NB, true, true, true>), dim3(T_m),
-                       dim3(DEC_THREADS), 0, st, M, NR, N, nbins, q, L, EW, CNT, NV, tim,
-                       ids, flg, (double*)nullptr, (int32_t*)nullptr);
-  hipLaunchKernelGGL((dec_npre::k_deciles<NB, true, true, false>), dim3(T_m),
-                     dim3(DEC_THREADS), 0, st, M, NR, N, nbins, q, L, EW, CNT, NV, tim,
-                     ids, flg, LS, ticket);
+    if (a.flg)
+      dec_launch(dec_npre::k_deciles<NB, true, true, true>, DEC_THREADS, a, a.flg, nullptr, nullptr);
+    dec_launch(dec_npre::k_deciles<NB, true, true, false>, DEC_THREADS, a, a.flg, a.LS, a.ticket);
+  });
 }
-
-#define INST(NB)                                                                              \
-  template void launch_deciles_pre_narrow<NB>(int, hipStream_t, const double*, const double*,  \
-                                              int64_t, int, const QTab&, int8_t*, double*,       \
-                                              int32_t*, int32_t*, int64_t*, uint16_t*,       \
-                                              int32_t*, double*, int32_t*);
-INST(0)
-INST(2)
-INST(3)
-INST(4)
-INST(5)
-INST(10)
-INST(20)
-#undef INST

@@ -2085,133 +2085,6 @@ __global__ __launch_bounds__(256) void k_fw_fold(const double* __restrict__ FWp,
   FWt[i] = tot;
 }
 
-// Returns whether the legs-only segment pass ran (its partials in the two-leg layout).
-template <int NB>
-static bool launch_cohort(hipStream_t st, const PfPlan& pl, const int8_t* L, const double* NR,
-                          const double* W, int T_m, int B, int64_t N, int K, double* SWRp,
-                          double* SWp, double* FWp, char* segws, int64_t perm_b, int64_t off_b,
-                          int64_t wsrt_b, bool legs, const PanAddr& pa, int64_t lm_b = 0) {
-  const dim3 g((unsigned)(pl.C * T_m * B));
-  if (g_tune_cohort_seg && segws && K * (NB + 1) <= SEG_MAXKD) {
-    uint16_t* PERM = (uint16_t*)(segws + perm_b);
-    int32_t* OFF = (int32_t*)(segws + off_b);
-    double* WSRT = (double*)(segws + wsrt_b);
-    SegJ sj;
-    sj.n = 1;
-    sj.PERM[0] = PERM; sj.OFF[0] = OFF; sj.SWR[0] = SWRp; sj.SW[0] = SWp;
-    const int xcd = pl.C == 1 && B >= 8;
-    const int64_t rows = (int64_t)T_m * B;
-    const int Cs = (int)std::min<int64_t>(pl.C, std::max<int64_t>(1, (1024 + rows - 1) / rows));
-    const dim3 g1((unsigned)(T_m * B)),
-        g2(xcd ? (unsigned)(8 * ((B + 7) / 8) * T_m) : (unsigned)(pl.C * T_m * B));
-    const size_t lds = (size_t)(N + 1) * sizeof(double) +
-                       (legs ? (size_t)K * 4 * sizeof(uint16_t) : (size_t)K * (NB + 1) * sizeof(int32_t));
-    if (legs) {
-      if (W) {
-        hipLaunchKernelGGL((k_label_sort<NB, true, true>), g1, dim3(PF_THREADS), (size_t)N * 9, st, L, W, N,
-                           pl.C, PERM, OFF, WSRT, FWp, pa);
-        hipLaunchKernelGGL((k_cohort_seg<NB, true, true>), g2, dim3(PF_THREADS), lds, st, NR, sj,
-                           (const double*)WSRT, T_m, B, N, K, pl.C, Cs, xcd, 1, pa, B);
-      } else {
-        if ((N & 3) == 0)   // one wave per row (C5's equal-weight legs)
-          hipLaunchKernelGGL((g_tune_ls_opt ? k_label_sort_legs_ew<NB, true> : k_label_sort_legs_ew<NB, false>), dim3((unsigned)((T_m * (int64_t)B + PF_WAVES - 1) / PF_WAVES)),
-                             dim3(PF_THREADS), 0, st, L, N, pl.C, (int64_t)T_m * B, PERM, OFF, FWp, pa,
-                             g_tune_turn_mask ? (uint64_t*)(segws + lm_b) : nullptr, (N + 255) / 256 * 4);
-        else
-          hipLaunchKernelGGL((k_label_sort<NB, false, true>), g1, dim3(PF_THREADS), (size_t)N, st, L, W, N,
-                             pl.C, PERM, OFF, WSRT, FWp, pa);
-        hipLaunchKernelGGL((k_cohort_seg<NB, false, true>), g2, dim3(PF_THREADS), lds, st, NR, sj,
-                           (const double*)WSRT, T_m, B, N, K, pl.C, Cs, xcd, 1, pa, B);
-      }
-    } else if (W) {
-      hipLaunchKernelGGL((k_label_sort<NB, true>), g1, dim3(PF_THREADS), (size_t)N * 9, st, L, W, N, pl.C,
-                         PERM, OFF, WSRT, FWp, pa);
-      hipLaunchKernelGGL((k_cohort_seg<NB, true>), g2, dim3(PF_THREADS), lds, st, NR, sj,
-                         (const double*)WSRT, T_m, B, N, K, pl.C, Cs, xcd, 1, pa, B);
-    } else {
-      hipLaunchKernelGGL((k_label_sort<NB, false>), g1, dim3(PF_THREADS), (size_t)N, st, L, W, N, pl.C,
-                         PERM, OFF, WSRT, FWp, pa);
-      hipLaunchKernelGGL((k_cohort_seg<NB, false>), g2, dim3(PF_THREADS), lds, st, NR, sj,
-                         (const double*)WSRT, T_m, B, N, K, pl.C, Cs, xcd, 1, pa, B);
-    }
-    return legs;
-  }
-  if (g_tune_cohort_lds && K * NB <= AC_MAXKD) {
-    const dim3 g2((unsigned)(pl.C * T_m * B));
-    if (W)
-      hipLaunchKernelGGL((k_cohort_lds<NB, true>), g2, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B,
-                         N, K, pl.C, pl.CH, SWRp, SWp, FWp, pa);
-    else
-      hipLaunchKernelGGL((k_cohort_lds<NB, false>), g2, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B,
-                         N, K, pl.C, pl.CH, SWRp, SWp, FWp, pa);
-    return false;
-  }
-  if (W)
-    hipLaunchKernelGGL((k_cohort<NB, true>), g, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B, N, K,
-                       pl.C, pl.CH, SWRp, SWp, FWp, pa);
-  else
-    hipLaunchKernelGGL((k_cohort<NB, false>), g, dim3(PF_THREADS), 0, st, L, NR, W, T_m, B, N, K,
-                       pl.C, pl.CH, SWRp, SWp, FWp, pa);
-  return false;
-}
-
-// Equal-weight cohort sums of nJ look-backs sharing one next_ret panel (segment path, one chunk
-// per row): each J's label sort, then ONE k_cohort_seg launch staging each month's return row
-// once for every J.  ws[q]: J q's workspace base; the partials land where launch_cohort puts
-// them, bit for bit the same values.
-// grouped: L[0] holds the Js' label panels group-major ([nJ][T_m][B * N]) and ws[0] is ONE
-// workspace laid out for nJ * B panels (J q's panel b = panel q * B + b, as csm_cohort_sums_grouped
-// lays them out): one label-sort launch for every J, and the same partials at those rows.
-template <int NB>
-static void launch_cohort_js(hipStream_t st, const PfPlan& pl, int nJ, const int8_t* const* L,
-                             const double* NR, int T_m, int B, int64_t N, int K, char* const* ws,
-                             int64_t swr_b, int64_t sw_b, int64_t fw_b, int64_t perm_b,
-                             int64_t off_b, bool legs, bool grouped, int64_t lm_b) {
-  const int xcd = B >= 8;
-  const dim3 g2(xcd ? (unsigned)(8 * ((B + 7) / 8) * T_m) : (unsigned)(T_m * B));
-  const PanAddr pa = pan_plain(B, N);
-  const int Bo = grouped ? nJ * B : B;   // panels per month of the workspace rows
-  auto label_sort = [&](const int8_t* Lq, char* w, int nrow_b, const PanAddr& pl_a) {
-    uint16_t* PERM = (uint16_t*)(w + perm_b);
-    int32_t* OFF = (int32_t*)(w + off_b);
-    double* FWp = (double*)(w + fw_b);
-    const int64_t rows = (int64_t)T_m * nrow_b;
-    if (legs && (N & 3) == 0)
-      hipLaunchKernelGGL((g_tune_ls_opt ? k_label_sort_legs_ew<NB, true> : k_label_sort_legs_ew<NB, false>),
-                         dim3((unsigned)((rows + PF_WAVES - 1) / PF_WAVES)),
-                         dim3(PF_THREADS), 0, st, Lq, N, 1, rows, PERM, OFF, FWp, pl_a,
-                         g_tune_turn_mask ? (uint64_t*)(w + lm_b) : nullptr, (N + 255) / 256 * 4);
-    else if (legs)
-      hipLaunchKernelGGL((k_label_sort<NB, false, true>), dim3((unsigned)rows), dim3(PF_THREADS), (size_t)N,
-                         st, Lq, (const double*)nullptr, N, 1, PERM, OFF, (double*)nullptr, FWp, pl_a);
-    else
-      hipLaunchKernelGGL((k_label_sort<NB, false>), dim3((unsigned)rows), dim3(PF_THREADS), (size_t)N, st,
-                         Lq, (const double*)nullptr, N, 1, PERM, OFF, (double*)nullptr, FWp, pl_a);
-  };
-  if (grouped) label_sort(L[0], ws[0], nJ * B, pan_grouped(nJ, B, T_m, N));
-  const int64_t PS = seg_stride(N);
-  SegJ sj;
-  sj.n = nJ;
-  for (int q = 0; q < nJ; ++q) {
-    char* w = grouped ? ws[0] : ws[q];
-    if (!grouped) label_sort(L[q], w, B, pa);
-    const int64_t r0 = grouped ? (int64_t)q * B : 0;   // J q's first workspace row of a month
-    sj.PERM[q] = (uint16_t*)(w + perm_b) + r0 * PS;
-    sj.OFF[q] = (int32_t*)(w + off_b) + r0 * (NB + 1);
-    const int swv = legs ? 2 : NB;   // partials per (row, age): k_cohort_seg's layout
-    sj.SWR[q] = (double*)(w + swr_b) + r0 * K * swv;   // (one cohort chunk)
-    sj.SW[q] = (double*)(w + sw_b) + r0 * K * swv;
-  }
-  const size_t lds = (size_t)(N + 1) * sizeof(double) +
-                     (legs ? (size_t)nJ * K * 4 * sizeof(uint16_t) : (size_t)nJ * K * (NB + 1) * sizeof(int32_t));
-  if (legs)
-    hipLaunchKernelGGL((k_cohort_seg<NB, false, true>), g2, dim3(PF_THREADS), lds, st, NR, sj,
-                       (const double*)nullptr, T_m, B, N, K, 1, 1, xcd, 1, pa, Bo);
-  else
-    hipLaunchKernelGGL((k_cohort_seg<NB, false>), g2, dim3(PF_THREADS), lds, st, NR, sj,
-                       (const double*)nullptr, T_m, B, N, K, 1, 1, xcd, 1, pa, Bo);
-}
-
 // Workspace layout of the cohort partials for (T_m, B, N, n_bins, Kmax): SWRp, SWp
 // [rows][Kmax][C][n_bins], FWp [rows][C][2], then the turnover partials [rows][Ct] x 2.
 struct PfLayout {
@@ -2262,6 +2135,129 @@ static PfLayout pf_layout(int32_t T_m, int32_t B, int64_t N, int32_t n_bins, int
   return l;
 }
 
+// cohort sums come compiled for these bin counts
+template <typename F>
+static bool cohort_nb_dispatch(int n_bins, F&& f) {
+  return nb_dispatch<2, 3, 4, 5, 10, 20, 30>(n_bins, f);
+}
+
+// The arguments of one cohort pass, filled once by its entry point: the workspace layout (the
+// plan and every offset), the return / weight panels every label panel of the pass shares, the
+// shapes, the legs flag and the panel addressing.  The label panel and the workspace base are
+// the launcher's own arguments: the shared-next_ret pass has one of each per look-back.
+struct CohortLaunch {
+  hipStream_t st;
+  PfLayout lay;
+  const double* NR;
+  const double* W;
+  int T_m, B;
+  int64_t N;
+  int K;
+  bool legs;
+  PanAddr pa;
+};
+
+// The label sort of `rows` rows into the workspace at ws (PERM, OFF, the formation weights; WSRT
+// with value weights).
+template <int NB, bool VW, bool LEGS>
+static void launch_label_sort(hipStream_t st, const PfLayout& lay, const int8_t* L, const double* W,
+                              int64_t N, int C, int64_t rows, char* ws, double* WSRT,
+                              const PanAddr& pa) {
+  uint16_t* PERM = (uint16_t*)(ws + lay.perm_b);
+  int32_t* OFF = (int32_t*)(ws + lay.off_b);
+  double* FWp = (double*)ws + lay.fw;
+  if (LEGS && !VW && (N & 3) == 0)   // one wave per row (C5's equal-weight legs)
+    hipLaunchKernelGGL((g_tune_ls_opt ? k_label_sort_legs_ew<NB, true> : k_label_sort_legs_ew<NB, false>),
+                       dim3((unsigned)((rows + PF_WAVES - 1) / PF_WAVES)), dim3(PF_THREADS), 0, st,
+                       L, N, C, rows, PERM, OFF, FWp, pa,
+                       g_tune_turn_mask ? (uint64_t*)(ws + lay.lm_b) : nullptr, (N + 255) / 256 * 4);
+  else
+    hipLaunchKernelGGL((k_label_sort<NB, VW, LEGS>), dim3((unsigned)rows), dim3(PF_THREADS),
+                       VW ? (size_t)N * 9 : (size_t)N, st, L, W, N, C, PERM, OFF, WSRT, FWp, pa);
+}
+
+// the label-sorted segment pass of one label panel: its sort, then the segment gathers
+template <int NB, bool VW, bool LEGS>
+static void launch_cohort_seg(const CohortLaunch& a, const int8_t* L, char* ws) {
+  const PfLayout& lay = a.lay;
+  const int C = lay.p.C;
+  double* WSRT = (double*)(ws + lay.wsrt_b);
+  SegJ sj;
+  sj.n = 1;
+  sj.PERM[0] = (uint16_t*)(ws + lay.perm_b);
+  sj.OFF[0] = (int32_t*)(ws + lay.off_b);
+  sj.SWR[0] = (double*)ws + lay.swr;
+  sj.SW[0] = (double*)ws + lay.sw;
+  const int xcd = C == 1 && a.B >= 8;
+  const int64_t rows = (int64_t)a.T_m * a.B;
+  const int Cs = (int)std::min<int64_t>(C, std::max<int64_t>(1, (1024 + rows - 1) / rows));
+  const dim3 g2(xcd ? (unsigned)(8 * ((a.B + 7) / 8) * a.T_m) : (unsigned)(C * a.T_m * a.B));
+  const size_t lds = (size_t)(a.N + 1) * sizeof(double) +
+                     (LEGS ? (size_t)a.K * 4 * sizeof(uint16_t) : (size_t)a.K * (NB + 1) * sizeof(int32_t));
+  launch_label_sort<NB, VW, LEGS>(a.st, lay, L, a.W, a.N, C, rows, ws, WSRT, a.pa);
+  hipLaunchKernelGGL((k_cohort_seg<NB, VW, LEGS>), g2, dim3(PF_THREADS), lds, a.st, a.NR, sj,
+                     (const double*)WSRT, a.T_m, a.B, a.N, a.K, C, Cs, xcd, 1, a.pa, a.B);
+}
+
+// The cohort sums of one label panel L into the workspace at ws.  Returns whether the legs-only
+// segment pass ran (its partials in the two-leg layout).
+template <int NB>
+static bool launch_cohort(const CohortLaunch& a, const int8_t* L, char* ws) {
+  if (g_tune_cohort_seg && a.lay.seg && a.K * (NB + 1) <= SEG_MAXKD) {
+    (a.legs ? (a.W ? launch_cohort_seg<NB, true, true> : launch_cohort_seg<NB, false, true>)
+            : (a.W ? launch_cohort_seg<NB, true, false> : launch_cohort_seg<NB, false, false>))(a, L, ws);
+    return a.legs;
+  }
+  const PfPlan& pl = a.lay.p;
+  const bool lds = g_tune_cohort_lds && a.K * NB <= AC_MAXKD;
+  hipLaunchKernelGGL((lds ? (a.W ? k_cohort_lds<NB, true> : k_cohort_lds<NB, false>)
+                          : (a.W ? k_cohort<NB, true> : k_cohort<NB, false>)),
+                     dim3((unsigned)(pl.C * a.T_m * a.B)), dim3(PF_THREADS), 0, a.st, L, a.NR, a.W,
+                     a.T_m, a.B, a.N, a.K, pl.C, pl.CH, (double*)ws + a.lay.swr,
+                     (double*)ws + a.lay.sw, (double*)ws + a.lay.fw, a.pa);
+  return false;
+}
+
+// Equal-weight cohort sums of nJ look-backs sharing one next_ret panel (segment path, one chunk
+// per row): each J's label sort, then ONE k_cohort_seg launch staging each month's return row
+// once for every J.  ws[q]: J q's workspace base; the partials land where launch_cohort puts
+// them, bit for bit the same values.
+// grouped: L[0] holds the Js' label panels group-major ([nJ][T_m][B * N]) and ws[0] is ONE
+// workspace laid out for nJ * B panels (J q's panel b = panel q * B + b, as csm_cohort_sums_grouped
+// lays them out): one label-sort launch for every J, and the same partials at those rows.
+template <int NB>
+static void launch_cohort_js(const CohortLaunch& a, int nJ, const int8_t* const* L, char* const* ws,
+                             bool grouped) {
+  const PfLayout& lay = a.lay;
+  const int B = a.B, K = a.K;
+  const int xcd = B >= 8;
+  const dim3 g2(xcd ? (unsigned)(8 * ((B + 7) / 8) * a.T_m) : (unsigned)(a.T_m * B));
+  const int Bo = grouped ? nJ * B : B;   // panels per month of the workspace rows
+  auto label_sort = [&](const int8_t* Lq, char* w, int nrow_b, const PanAddr& pl_a) {
+    (a.legs ? launch_label_sort<NB, false, true> : launch_label_sort<NB, false, false>)(
+        a.st, lay, Lq, nullptr, a.N, 1, (int64_t)a.T_m * nrow_b, w, nullptr, pl_a);
+  };
+  if (grouped) label_sort(L[0], ws[0], nJ * B, pan_grouped(nJ, B, a.T_m, a.N));
+  const int64_t PS = seg_stride(a.N);
+  SegJ sj;
+  sj.n = nJ;
+  for (int q = 0; q < nJ; ++q) {
+    char* w = grouped ? ws[0] : ws[q];
+    if (!grouped) label_sort(L[q], w, B, a.pa);
+    const int64_t r0 = grouped ? (int64_t)q * B : 0;   // J q's first workspace row of a month
+    sj.PERM[q] = (uint16_t*)(w + lay.perm_b) + r0 * PS;
+    sj.OFF[q] = (int32_t*)(w + lay.off_b) + r0 * (NB + 1);
+    const int swv = a.legs ? 2 : NB;   // partials per (row, age): k_cohort_seg's layout
+    sj.SWR[q] = (double*)w + lay.swr + r0 * K * swv;   // (one cohort chunk)
+    sj.SW[q] = (double*)w + lay.sw + r0 * K * swv;
+  }
+  const size_t lds = (size_t)(a.N + 1) * sizeof(double) +
+                     (a.legs ? (size_t)nJ * K * 4 * sizeof(uint16_t) : (size_t)nJ * K * (NB + 1) * sizeof(int32_t));
+  hipLaunchKernelGGL((a.legs ? k_cohort_seg<NB, false, true> : k_cohort_seg<NB, false, false>), g2,
+                     dim3(PF_THREADS), lds, a.st, a.NR, sj, (const double*)nullptr, a.T_m, B, a.N, K,
+                     1, 1, xcd, 1, a.pa, Bo);
+}
+
 // this file's knobs (csm_tune forwards every key that is not in its own table)
 static const TuneKnob g_knobs[] = {
     {"cohort_lds", &g_tune_cohort_lds, [](int v) { return v == 0 || v == 1; }},
@@ -2305,22 +2301,19 @@ static int cohort_sums(csm_ctx* ctx, const int8_t* L, const double* NR, const do
     return set_err(ctx, CSM_E_INVAL, "csm_cohort_sums: bad arguments (T_m=%d B=%d N=%lld Kmax=%d)",
                    T_m, B, (long long)N, Kmax);
   if (T_m == 0) return CSM_OK;
-  const PfLayout lay = pf_layout(T_m, B, N, n_bins, Kmax);
+  const CohortLaunch a{ctx->stream, pf_layout(T_m, B, N, n_bins, Kmax), NR, W, T_m, B, N, Kmax, legs, pa};
+  const PfLayout& lay = a.lay;
   double* ws = (double*)workspace;
-  hipStream_t st = ctx->stream;
   bool dense = false;   // legs-only partials in the two-leg layout
-  switch (n_bins) {
-#define PF_CASE(NBV) case NBV: dense = launch_cohort<NBV>(st, lay.p, L, NR, W, T_m, B, N, Kmax, ws + lay.swr, ws + lay.sw, ws + lay.fw, lay.seg ? (char*)workspace : nullptr, lay.perm_b, lay.off_b, lay.wsrt_b, legs, pa, lay.lm_b); break;
-    PF_CASE(2) PF_CASE(3) PF_CASE(4) PF_CASE(5) PF_CASE(10) PF_CASE(20) PF_CASE(30)
-#undef PF_CASE
-    default:
-      return set_err(ctx, CSM_E_INVAL, "csm_cohort_sums: n_bins=%d unsupported (2,3,4,5,10,20,30)", n_bins);
-  }
+  if (!cohort_nb_dispatch(n_bins, [&](auto nb) {
+        dense = launch_cohort<decltype(nb)::value>(a, L, (char*)workspace);
+      }))
+    return set_err(ctx, CSM_E_INVAL, "csm_cohort_sums: n_bins=%d unsupported (2,3,4,5,10,20,30)", n_bins);
   LAUNCH_CHECK(ctx, "k_cohort");
-  fill_i32(st, (int32_t*)((char*)workspace + lay.lw_b), 1, dense ? 2 : n_bins);
+  fill_i32(a.st, (int32_t*)((char*)workspace + lay.lw_b), 1, dense ? 2 : n_bins);
   planes_note(ctx, workspace, !W && legs_masks(lay, legs, N, Kmax, n_bins) ? 1u : 0u);
   if (lay.p.C > 1) {
-    hipLaunchKernelGGL(k_fw_fold, dim3((unsigned)((2 * lay.rows + 255) / 256)), dim3(256), 0, st,
+    hipLaunchKernelGGL(k_fw_fold, dim3((unsigned)((2 * lay.rows + 255) / 256)), dim3(256), 0, a.st,
                        (const double*)(ws + lay.fw), lay.rows, lay.p.C, ws + lay.fwt);
     LAUNCH_CHECK(ctx, "k_fw_fold");
   }
@@ -2348,13 +2341,18 @@ int csm_cohort_sums_js(csm_ctx* ctx, int32_t nJ, const int8_t* const* L, const d
     if (!L[q] || !workspaces[q])
       return set_err(ctx, CSM_E_INVAL, "csm_cohort_sums_js: L[%d] or workspace[%d] is NULL", q, q);
   if (T_m == 0) return CSM_OK;
-  const PfLayout lay = pf_layout(T_m, B, N, n_bins, Kmax);
+  const CohortLaunch a{ctx->stream, pf_layout(T_m, B, N, n_bins, Kmax), NR, nullptr, T_m, B, N, Kmax,
+                       legs != 0, pan_plain(B, N)};
+  const PfLayout& lay = a.lay;
+  char* ws[SEG_MAXJ];
+  for (int q = 0; q < nJ; ++q) ws[q] = (char*)workspaces[q];
   // one staged return row for every J: the segment path with one chunk per row; otherwise the
   // per-J passes (the same partials)
   const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 &&
                       (legs ? nJ * Kmax * 4 : nJ * Kmax * (n_bins + 1)) <= SEG_MAXKD &&
-                      (n_bins == 2 || n_bins == 3 || n_bins == 4 || n_bins == 5 || n_bins == 10 ||
-                       n_bins == 20 || n_bins == 30);
+                      cohort_nb_dispatch(n_bins, [&](auto nb) {
+                        launch_cohort_js<decltype(nb)::value>(a, nJ, L, ws, false);
+                      });
   if (!shared) {
     for (int q = 0; q < nJ; ++q) {
       r = cohort_sums(ctx, L[q], NR, nullptr, T_m, B, N, n_bins, Kmax, workspaces[q], legs != 0,
@@ -2363,17 +2361,9 @@ int csm_cohort_sums_js(csm_ctx* ctx, int32_t nJ, const int8_t* const* L, const d
     }
     return CSM_OK;
   }
-  hipStream_t st = ctx->stream;
-  char* ws[SEG_MAXJ];
-  for (int q = 0; q < nJ; ++q) ws[q] = (char*)workspaces[q];
-  switch (n_bins) {
-#define PJ_CASE(NBV) case NBV: launch_cohort_js<NBV>(st, lay.p, nJ, L, NR, T_m, B, N, Kmax, ws, lay.swr * 8, lay.sw * 8, lay.fw * 8, lay.perm_b, lay.off_b, legs != 0, false, lay.lm_b); break;
-    PJ_CASE(2) PJ_CASE(3) PJ_CASE(4) PJ_CASE(5) PJ_CASE(10) PJ_CASE(20) PJ_CASE(30)
-#undef PJ_CASE
-  }
   LAUNCH_CHECK(ctx, "k_cohort_seg (shared next_ret)");
   for (int q = 0; q < nJ; ++q)
-    fill_i32(st, (int32_t*)(ws[q] + lay.lw_b), 1, legs ? 2 : n_bins);
+    fill_i32(a.st, (int32_t*)(ws[q] + lay.lw_b), 1, legs ? 2 : n_bins);
   for (int q = 0; q < nJ; ++q) planes_note(ctx, ws[q], legs_masks(lay, legs != 0, N, Kmax, n_bins) ? 1u : 0u);
   // (the shared path has one cohort chunk: each J's partials are its folded totals)
   return CSM_OK;
@@ -2392,23 +2382,21 @@ int csm_cohort_sums_js_grouped(csm_ctx* ctx, int32_t nJ, const int8_t* L, const 
     return set_err(ctx, CSM_E_INVAL, "csm_cohort_sums_js_grouped: legs on rows of <= %d assets "
                    "(N=%lld)", SEG_MAXN, (long long)N);
   if (T_m == 0) return CSM_OK;
-  const PfLayout lay = pf_layout(T_m, nJ * B, N, n_bins, Kmax);
+  // (the layout of the nJ * B panels' workspace; B and the addressing are one look-back's)
+  const CohortLaunch a{ctx->stream, pf_layout(T_m, nJ * B, N, n_bins, Kmax), NR, nullptr, T_m, B, N,
+                       Kmax, legs != 0, pan_plain(B, N)};
+  const PfLayout& lay = a.lay;
+  char* ws = (char*)workspace;
   const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 &&
                       (legs ? nJ * Kmax * 4 : nJ * Kmax * (n_bins + 1)) <= SEG_MAXKD &&
-                      (n_bins == 2 || n_bins == 3 || n_bins == 4 || n_bins == 5 || n_bins == 10 ||
-                       n_bins == 20 || n_bins == 30);
+                      cohort_nb_dispatch(n_bins, [&](auto nb) {
+                        launch_cohort_js<decltype(nb)::value>(a, nJ, &L, &ws, true);
+                      });
   if (!shared)   // the grouped pass with every group reading the one next_ret block
     return cohort_sums(ctx, L, NR, nullptr, T_m, nJ * B, N, n_bins, Kmax, workspace, legs != 0,
                        pan_grouped(nJ, B, T_m, N, true));
-  hipStream_t st = ctx->stream;
-  char* ws = (char*)workspace;
-  switch (n_bins) {
-#define PJ_CASE(NBV) case NBV: launch_cohort_js<NBV>(st, lay.p, nJ, &L, NR, T_m, B, N, Kmax, &ws, lay.swr * 8, lay.sw * 8, lay.fw * 8, lay.perm_b, lay.off_b, legs != 0, true, lay.lm_b); break;
-    PJ_CASE(2) PJ_CASE(3) PJ_CASE(4) PJ_CASE(5) PJ_CASE(10) PJ_CASE(20) PJ_CASE(30)
-#undef PJ_CASE
-  }
   LAUNCH_CHECK(ctx, "k_cohort_seg (shared next_ret, grouped)");
-  fill_i32(st, (int32_t*)(ws + lay.lw_b), 1, legs ? 2 : n_bins);
+  fill_i32(a.st, (int32_t*)(ws + lay.lw_b), 1, legs ? 2 : n_bins);
   planes_note(ctx, workspace, legs_masks(lay, legs != 0, N, Kmax, n_bins) ? 1u : 0u);
   return CSM_OK;
 }

@@ -510,6 +510,36 @@ class Engine:
                    _ptr(PR), _ptr(LS), _ptr(TURN), _ptr(COST), _ptr(NET), _ptr(workspace))
         return PortfolioOut(PR=PR, LS=LS, TURN=TURN, COST=COST, NET=NET)
 
+    def _cohort_pass(self, T_m, BN, B, panels, n_bins, Ks, legs_only, need_full, run, bname="B"):
+        """What the portfolio_multi* wrappers share.  Rows of BN cells are B panels of N assets
+        (ValueError otherwise); legs_only holds only for rows of <= LEGS_MAX_N assets (wider
+        rows: every decile).  run(N, Ks, Kmax, ws, legs_only, flag) checks its tensors, makes the
+        cohort pass and its accounting, and returns the wrapper's result; ws(given=None) is a
+        workspace for `panels` panels (`given` when it is large enough).  legs_only with
+        need_full None: the pass gets a flag of its own, the flag is read back (the one device
+        sync), and when it is set -- a panel lacks a leg's column -- run is repeated without
+        legs."""
+        if B < 1 or BN % B:
+            raise ValueError(f"row width {BN} is not {bname}={B} panels")
+        N = BN // B
+        Ks = [int(k) for k in Ks]
+        Kmax = max(Ks)
+        legs_only = bool(legs_only) and N <= LEGS_MAX_N
+
+        def ws(given=None):
+            nbytes = int(self.lib.csm_portfolio_workspace(T_m, int(panels), N, int(n_bins), Kmax))
+            if given is None or given.numel() * given.element_size() < nbytes:
+                given = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
+            return given
+
+        flag = need_full
+        if legs_only and need_full is None:
+            flag = torch.zeros(1, dtype=torch.int32, device=self.device)
+        out = run(N, Ks, Kmax, ws, legs_only, flag)
+        if legs_only and need_full is None and int(flag.item()):
+            out = run(N, Ks, Kmax, ws, False, None)
+        return out
+
     def portfolio_multi(self, L, NR, n_bins=10, Ks=(1,), W=None, B=1, half_spread=0.0005,
                         k_impact=0.1, aum=0.0, ADV=None, SIG=None, with_costs=True,
                         workspace=None, return_stacked=False, legs_only=False, need_full=None):
@@ -522,33 +552,21 @@ class Engine:
         need_full (device int32 [1], caller-zeroed) the flag is left there instead, no sync, and
         the caller reruns with legs_only=False when it is set."""
         T_m, BN = L.shape
-        if B < 1 or BN % B:
-            raise ValueError(f"row width {BN} is not B={B} panels")
-        N = BN // B
-        _need(L, "L", torch.int8, (T_m, BN), self.device)
-        _need(NR, "NR", torch.float64, (T_m, BN), self.device)
-        for t, nm in ((W, "W"), (ADV, "ADV"), (SIG, "SIG")):
-            if t is not None:
-                _need(t, nm, torch.float64, (T_m, BN), self.device)
-        Ks = [int(k) for k in Ks]
-        Kmax = max(Ks)
-        legs_only = bool(legs_only) and N <= LEGS_MAX_N   # wider rows: every decile
-        nbytes = int(self.lib.csm_portfolio_workspace(T_m, B, N, int(n_bins), Kmax))
-        if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
-            workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
-        self._call("csm_cohort_sums_legs" if legs_only else "csm_cohort_sums", _ptr(L), _ptr(NR),
-                   _ptr(W), T_m, int(B), N, int(n_bins), Kmax, _ptr(workspace))
-        flag = need_full
-        if legs_only and need_full is None:
-            flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        res, stacked = self._from_cohorts(L, W, T_m, B, N, n_bins, Ks, half_spread, k_impact,
-                                          aum, ADV, SIG, with_costs, workspace, legs_only, flag)
-        if legs_only and need_full is None and int(flag.item()):   # a panel lacks a leg's column
-            return self.portfolio_multi(L, NR, n_bins, Ks, W, B, half_spread, k_impact, aum,
-                                        ADV, SIG, with_costs, workspace, return_stacked)
-        if return_stacked:
-            return res, stacked
-        return res
+
+        def run(N, Ks, Kmax, ws, legs, flag):
+            _need(L, "L", torch.int8, (T_m, BN), self.device)
+            _need(NR, "NR", torch.float64, (T_m, BN), self.device)
+            for t, nm in ((W, "W"), (ADV, "ADV"), (SIG, "SIG")):
+                if t is not None:
+                    _need(t, nm, torch.float64, (T_m, BN), self.device)
+            w = ws(workspace)
+            self._call("csm_cohort_sums_legs" if legs else "csm_cohort_sums", _ptr(L), _ptr(NR),
+                       _ptr(W), T_m, int(B), N, int(n_bins), Kmax, _ptr(w))
+            return self._from_cohorts(L, W, T_m, B, N, n_bins, Ks, half_spread, k_impact, aum,
+                                      ADV, SIG, with_costs, w, legs, flag)
+
+        res, stacked = self._cohort_pass(T_m, BN, B, B, n_bins, Ks, legs_only, need_full, run)
+        return (res, stacked) if return_stacked else res
 
     def portfolio_multi_js(self, Ls, NR, n_bins=10, Ks=(1,), B=1, half_spread=0.0005,
                            k_impact=0.1, aum=0.0, with_costs=True, legs_only=False, need_full=None):
@@ -558,31 +576,21 @@ class Engine:
         Returns [(res, stacked)] per J, each equal bit for bit to portfolio_multi(L, NR, ...,
         return_stacked=True)."""
         T_m, BN = NR.shape
-        if B < 1 or BN % B:
-            raise ValueError(f"row width {BN} is not B={B} panels")
-        N = BN // B
-        _need(NR, "NR", torch.float64, (T_m, BN), self.device)
-        for L in Ls:
-            _need(L, "L", torch.int8, (T_m, BN), self.device)
-        Ks = [int(k) for k in Ks]
-        Kmax = max(Ks)
-        legs_only = bool(legs_only) and N <= LEGS_MAX_N
-        nbytes = int(self.lib.csm_portfolio_workspace(T_m, B, N, int(n_bins), Kmax))
-        wss = [torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device) for _ in Ls]
         nJ = len(Ls)
-        self._call("csm_cohort_sums_js", nJ, (ctypes.c_void_p * nJ)(*[L.data_ptr() for L in Ls]),
-                   _ptr(NR), T_m, int(B), N, int(n_bins), Kmax, 1 if legs_only else 0,
-                   (ctypes.c_void_p * nJ)(*[w.data_ptr() for w in wss]))
-        flag = need_full
-        if legs_only and need_full is None:
-            flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        outs = [self._from_cohorts(L, None, T_m, B, N, n_bins, Ks, half_spread, k_impact, aum,
-                                   None, None, with_costs, ws, legs_only, flag)
-                for L, ws in zip(Ls, wss)]
-        if legs_only and need_full is None and int(flag.item()):   # a panel lacks a leg's column
-            return self.portfolio_multi_js(Ls, NR, n_bins, Ks, B, half_spread, k_impact, aum,
-                                           with_costs, legs_only=False)
-        return outs
+
+        def run(N, Ks, Kmax, ws, legs, flag):
+            _need(NR, "NR", torch.float64, (T_m, BN), self.device)
+            for L in Ls:
+                _need(L, "L", torch.int8, (T_m, BN), self.device)
+            wss = [ws() for _ in Ls]
+            self._call("csm_cohort_sums_js", nJ, (ctypes.c_void_p * nJ)(*[L.data_ptr() for L in Ls]),
+                       _ptr(NR), T_m, int(B), N, int(n_bins), Kmax, 1 if legs else 0,
+                       (ctypes.c_void_p * nJ)(*[w.data_ptr() for w in wss]))
+            return [self._from_cohorts(L, None, T_m, B, N, n_bins, Ks, half_spread, k_impact, aum,
+                                       None, None, with_costs, w, legs, flag)
+                    for L, w in zip(Ls, wss)]
+
+        return self._cohort_pass(T_m, BN, B, B, n_bins, Ks, legs_only, need_full, run)
 
     def portfolio_plan(self, T_m, B, N, n_bins=10, K=1):
         """csm_portfolio_plan: (cohort chunks, turnover chunks) of a portfolio call; calls with
@@ -604,27 +612,17 @@ class Engine:
         if Lg.dim() != 3:
             raise ValueError("Lg must be [nJ][T_m][B * N]")
         nJ, T_m, BN = Lg.shape
-        if B < 1 or BN % B:
-            raise ValueError(f"row width {BN} is not B={B} panels")
-        N = BN // B
-        _need(Lg, "Lg", torch.int8, (nJ, T_m, BN), self.device)
-        _need(NR, "NR", torch.float64, (T_m, BN), self.device)
-        Ks = [int(k) for k in Ks]
-        Kmax = max(Ks)
-        legs_only = bool(legs_only) and N <= LEGS_MAX_N
-        nbytes = int(self.lib.csm_portfolio_workspace(T_m, nJ * B, N, int(n_bins), Kmax))
-        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
-        self._call("csm_cohort_sums_js_grouped", nJ, _ptr(Lg), _ptr(NR), T_m, int(B), N,
-                   int(n_bins), Kmax, 1 if legs_only else 0, _ptr(ws))
-        flag = need_full
-        if legs_only and need_full is None:
-            flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        res, stacked = self._from_cohorts(Lg, None, T_m, nJ * B, N, n_bins, Ks, half_spread,
-                                          k_impact, aum, None, None, with_costs, ws, legs_only,
-                                          flag, groups=(nJ, B))
-        if legs_only and need_full is None and int(flag.item()):   # a panel lacks a leg's column
-            return self.portfolio_multi_js_grouped(Lg, NR, n_bins, Ks, B, half_spread, k_impact,
-                                                   aum, with_costs, False, None, return_stacked)
+
+        def run(N, Ks, Kmax, ws, legs, flag):
+            _need(Lg, "Lg", torch.int8, (nJ, T_m, BN), self.device)
+            _need(NR, "NR", torch.float64, (T_m, BN), self.device)
+            w = ws()
+            self._call("csm_cohort_sums_js_grouped", nJ, _ptr(Lg), _ptr(NR), T_m, int(B), N,
+                       int(n_bins), Kmax, 1 if legs else 0, _ptr(w))
+            return self._from_cohorts(Lg, None, T_m, nJ * B, N, n_bins, Ks, half_spread, k_impact,
+                                      aum, None, None, with_costs, w, legs, flag, groups=(nJ, B))
+
+        res, stacked = self._cohort_pass(T_m, BN, B, nJ * B, n_bins, Ks, legs_only, need_full, run)
         return (res, stacked) if return_stacked else res
 
     def portfolio_multi_grouped(self, Lg, NRg, n_bins=10, Ks=(1,), W=None, Bg=1,
@@ -640,36 +638,22 @@ class Engine:
         if Lg.dim() != 3:
             raise ValueError("Lg must be [G][T_m][Bg * N]")
         G, T_m, BgN = Lg.shape
-        if Bg < 1 or BgN % Bg:
-            raise ValueError(f"row width {BgN} is not Bg={Bg} panels")
-        N = BgN // Bg
-        B = G * Bg
-        _need(Lg, "Lg", torch.int8, (G, T_m, BgN), self.device)
-        _need(NRg, "NRg", torch.float64, (G, T_m, BgN), self.device)
-        for t, nm in ((W, "W"), (ADV, "ADV"), (SIG, "SIG")):
-            if t is not None:
-                _need(t, nm, torch.float64, (T_m, BgN), self.device)
-        Ks = [int(k) for k in Ks]
-        Kmax = max(Ks)
-        legs_only = bool(legs_only) and N <= LEGS_MAX_N
-        nbytes = int(self.lib.csm_portfolio_workspace(T_m, B, N, int(n_bins), Kmax))
-        if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
-            workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
-        self._call("csm_cohort_sums_grouped", G, _ptr(Lg), _ptr(NRg), _ptr(W), T_m, int(Bg), N,
-                   int(n_bins), Kmax, 1 if legs_only else 0, _ptr(workspace))
-        flag = need_full
-        if legs_only and need_full is None:
-            flag = torch.zeros(1, dtype=torch.int32, device=self.device)
-        res, stacked = self._from_cohorts(Lg, W, T_m, B, N, n_bins, Ks, half_spread, k_impact,
-                                          aum, ADV, SIG, with_costs, workspace, legs_only, flag,
-                                          groups=(G, Bg))
-        if legs_only and need_full is None and int(flag.item()):   # a panel lacks a leg's column
-            return self.portfolio_multi_grouped(Lg, NRg, n_bins, Ks, W, Bg, half_spread, k_impact,
-                                                aum, ADV, SIG, with_costs, workspace,
-                                                return_stacked)
-        if return_stacked:
-            return res, stacked
-        return res
+
+        def run(N, Ks, Kmax, ws, legs, flag):
+            _need(Lg, "Lg", torch.int8, (G, T_m, BgN), self.device)
+            _need(NRg, "NRg", torch.float64, (G, T_m, BgN), self.device)
+            for t, nm in ((W, "W"), (ADV, "ADV"), (SIG, "SIG")):
+                if t is not None:
+                    _need(t, nm, torch.float64, (T_m, BgN), self.device)
+            w = ws(workspace)
+            self._call("csm_cohort_sums_grouped", G, _ptr(Lg), _ptr(NRg), _ptr(W), T_m, int(Bg), N,
+                       int(n_bins), Kmax, 1 if legs else 0, _ptr(w))
+            return self._from_cohorts(Lg, W, T_m, G * Bg, N, n_bins, Ks, half_spread, k_impact,
+                                      aum, ADV, SIG, with_costs, w, legs, flag, groups=(G, Bg))
+
+        res, stacked = self._cohort_pass(T_m, BgN, Bg, G * Bg, n_bins, Ks, legs_only, need_full,
+                                         run, bname="Bg")
+        return (res, stacked) if return_stacked else res
 
     def _from_cohorts(self, L, W, T_m, B, N, n_bins, Ks, half_spread, k_impact, aum, ADV, SIG,
                       with_costs, workspace, legs_only, need_full, groups=None):

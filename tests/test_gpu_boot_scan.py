@@ -194,3 +194,20 @@ def test_boot_scan_rejects_bad_args(engine):
     R2 = _base_returns(engine, 501, T_d=700)
     with pytest.raises(csmom.CsmError):
         engine.boot_scan(R2, 2, (3,), 1, with_ids=False)   # odd N
+
+
+def test_cohort_sums_reject_unsupported_n_bins(engine):
+    """csm_cohort_sums and csm_cohort_sums_js (two look-backs) come compiled for n_bins in
+    {2, 3, 4, 5, 10, 20, 30}: n_bins = 7 returns CSM_E_INVAL."""
+    import csmom
+    from csmom._lib import CSM_E_INVAL
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(21)
+    L = torch.randint(-1, 7, (24, 64), generator=g, device="cuda:0", dtype=torch.int8)
+    NR = torch.randn((24, 64), generator=g, device="cuda:0", dtype=torch.float64) * 0.1
+    for call in (lambda: engine.portfolio_multi(L, NR, 7, Ks=(3,)),
+                 lambda: engine.portfolio_multi_js([L, L.clone()], NR, 7, Ks=(3,))):
+        with pytest.raises(csmom.CsmError) as e:
+            call()
+        assert e.value.status == CSM_E_INVAL
+        assert "n_bins=7" in engine.lib.csm_last_error(engine.ctx).decode()

@@ -600,3 +600,101 @@ def test_multi_chunked_scan_rejects_bad_args(engine):
         engine.momentum_multi(pm, (16,), 1, chunks=4)             # max(J) + skip > 16
     with pytest.raises(csmom.CsmError):
         engine.momentum_multi(_up(_month_panel(999, 120, 5)), (3,), 1, chunks=4)   # odd N
+
+
+# ---- host dispatch: the n_bins -> compiled NB choice and the context buffers under capture
+
+@pytest.mark.parametrize("knobs", [{}, {"dec_narrow_max": 0, "dec_split": 0},
+                                   {"dec_narrow_max": 0, "dec_split": 1}],
+                         ids=["narrow", "wide_merged", "wide_split"])
+def test_deciles_n_bins_outside_compiled_list(engine, knobs):
+    """n_bins = 7 is not a compiled bin count.  Labels only (no next_ret) every n_bins runs:
+    csm_deciles and csm_deciles_ids give the oracle's labels.  With next_ret both return
+    CSM_E_INVAL and the message names the entry point and the bin count.  On the narrow kernels,
+    the wide ones with the merged pass, and the split launcher."""
+    import csmom
+    from csmom._lib import CSM_E_INVAL
+    rng = np.random.default_rng(3)
+    x = rng.normal(0.05, 0.3, (3, 256))
+    x[rng.random(x.shape) < 0.05] = np.nan
+    nr = rng.normal(0.01, 0.1, x.shape)
+    M, NR, IDS = _up(x), _up(nr), _ids_dev(x)
+    refL = O.assign_deciles(x, 7)
+    lib = engine.lib
+    try:
+        for k, v in knobs.items():
+            assert lib.csm_tune(k.encode(), v) == 0
+        assert np.array_equal(engine.deciles(M, None, 7)[0].cpu().numpy(), refL)
+        assert np.array_equal(engine.deciles_ids(M, None, IDS, 7)[0].cpu().numpy(), refL)
+        for name, call in (("csm_deciles", lambda: engine.deciles(M, NR, 7)),
+                           ("csm_deciles_ids", lambda: engine.deciles_ids(M, NR, IDS, 7))):
+            with pytest.raises(csmom.CsmError) as e:
+                call()
+            assert e.value.status == CSM_E_INVAL
+            msg = lib.csm_last_error(engine.ctx).decode()
+            assert msg.startswith(name + ":") and "n_bins=7" in msg, msg
+    finally:
+        lib.csm_tune(b"dec_narrow_max", 16384)
+        lib.csm_tune(b"dec_split", 2)
+
+
+def test_pipeline_buffer_growth_refused_under_capture():
+    """A fresh context has no bucket-id scratch.  csm_pipeline on the id path (N = 16388: N % 4
+    == 0, just above dec_narrow_max) while the stream is capturing returns CSM_E_INVAL, says to
+    run the call once first, and launches nothing; after one eager call the same capture
+    succeeds and its replay equals the eager outputs bit for bit."""
+    import csmom
+    from csmom._lib import CSM_E_INVAL
+    from oracle.synth_np import make_panel
+    pan = make_panel(16388, 260, seed=9, start="1990-01-01", with_volume=False, cents=True)
+    ms_h = pan["month_start"].astype(np.int64)
+    P, ms = _up(pan["P"]), _up(ms_h)
+    T_m, N = len(ms_h) - 1, P.shape[1]
+    days = np.diff(ms_h)
+    eng = csmom.Engine(0)
+
+    def bufs():
+        b = [eng.empty((T_m, N)) for _ in range(4)] + [
+            eng.empty((T_m, N), torch.int8), eng.empty((T_m, 10)),
+            eng.empty((T_m, 10), torch.int32), eng.empty((T_m,), torch.int32), eng.empty((T_m,))]
+        for t in b:
+            t.fill_(77)
+        return b
+
+    def run(out):
+        return eng.pipeline(P, ms, 3, 1, 10, max_month_days=int(days.max()),   # (12 months: J = 3)
+                            min_month_days=int(days.min()), out=out)
+
+    first, eager, replayed = bufs(), bufs(), bufs()
+    marker = torch.zeros(1, device="cuda:0")
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with pytest.raises(csmom.CsmError) as e:
+        with torch.cuda.graph(graph):
+            marker.add_(1)   # (the capture is not empty)
+            run(first)
+    assert e.value.status == CSM_E_INVAL
+    msg = eng.lib.csm_last_error(eng.ctx).decode()
+    assert msg.startswith("csm_pipeline:") and "run the call once before capturing" in msg, msg
+    del graph
+    torch.cuda.synchronize()
+    assert all(bool((t == 77).all()) for t in first)   # nothing was launched
+
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        run(eager)
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        run(replayed)
+    graph.replay()
+    torch.cuda.synchronize()
+    for a, b in zip(replayed[:4] + replayed[5:6] + replayed[8:], eager[:4] + eager[5:6] + eager[8:]):
+        assert bits_equal(a.cpu().numpy(), b.cpu().numpy())
+    for i in (4, 6, 7):   # labels, counts, ranked rows
+        assert torch.equal(replayed[i], eager[i])
+    assert bool((replayed[4] >= 0).any()) and bool(torch.isfinite(replayed[8]).any())
+    del graph
+    torch.cuda.synchronize()
