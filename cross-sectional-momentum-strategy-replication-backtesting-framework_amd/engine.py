@@ -85,6 +85,13 @@ class PortfolioOut:
 
 
 @dataclass
+class DailyOut:
+    DR: torch.Tensor                  # [T_d][n_bins] daily returns of the bins (NaN = no portfolio)
+    DLS: torch.Tensor                 # [T_d] top minus bottom (NaN if either leg is)
+    DCNT: torch.Tensor | None = None  # [T_m][K][n_bins] int32 member counts
+
+
+@dataclass
 class ShardState:
     """signal_shard's end-state record [5][N] (present months, pending ranked row, its
     subset-ffilled price, first / last present month) with the daily panel it came from
@@ -698,6 +705,56 @@ class Engine:
         out = self.empty((nS, B, 7))
         self._call("csm_summary", _ptr(LS), _ptr(TURN), _ptr(COST), _ptr(NET), nS, T_m, B,
                    float(freq), _ptr(out))
+        return out
+
+    def _refuse_capture(self, what):
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{what} is not supported under stream capture")
+
+    def daily_returns(self, P, month_start, L, NR, n_bins=10, K=1, W=None, max_month_days=None,
+                      out=None, workspace=None) -> DailyOut:
+        """csm_daily_returns (rule E7): the daily return series of the n_bins portfolios and of
+        top minus bottom for the labels L / next returns NR of the same panel (K overlapping
+        cohorts, equal weights or W), one pass over P.  out = (DR, DLS, DCNT)."""
+        self._refuse_capture("Engine.daily_returns")
+        T_d, N = P.shape
+        T_m = month_start.numel() - 1
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        _need(L, "L", torch.int8, (T_m, N), self.device)
+        _need(NR, "NR", torch.float64, (T_m, N), self.device)
+        if W is not None:
+            _need(W, "W", torch.float64, (T_m, N), self.device)
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        if out is None:
+            DR, DLS = self.empty((T_d, n_bins)), self.empty((T_d,))
+            DCNT = self.empty((T_m, K, n_bins), torch.int32)
+        else:
+            DR, DLS, DCNT = out
+            _need(DR, "DR", torch.float64, (T_d, n_bins), self.device)
+            _need(DLS, "DLS", torch.float64, (T_d,), self.device)
+            if DCNT is not None:
+                _need(DCNT, "DCNT", torch.int32, (T_m, K, n_bins), self.device)
+        nbytes = int(self.lib.csm_daily_workspace(T_d, N, T_m, int(n_bins), int(K)))
+        if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+            workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
+        self._call("csm_daily_returns", _ptr(P), T_d, N, _ptr(month_start), T_m,
+                   int(max_month_days), _ptr(L), _ptr(NR), _ptr(W), int(n_bins), int(K), _ptr(DR),
+                   _ptr(DLS), _ptr(DCNT), _ptr(workspace))
+        return DailyOut(DR=DR, DLS=DLS, DCNT=DCNT)
+
+    def series_stats(self, X, freq=252.0):
+        """csm_series_stats: [nS][6] (count, mean, Sharpe, annualised volatility, maximum
+        drawdown, final cumulative value) of the columns of X [T][nS] (or of one series [T]),
+        NaN entries dropped."""
+        self._refuse_capture("Engine.series_stats")
+        if X.dim() == 1:
+            X = X.unsqueeze(1)
+        T, nS = X.shape
+        _need(X, "X", torch.float64, (T, nS), self.device)
+        out = self.empty((nS, 6))
+        self._call("csm_series_stats", _ptr(X), nS, T, nS, float(freq), _ptr(out))
         return out
 
     def turnover_features(self, PM, VOL, so, mcap, lookback=3):

@@ -15,7 +15,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .features import compute_monthly_turnover, get_engine, monthly_signal
+from .features import compute_monthly_turnover, get_engine, monthly_signal, upload_panel
 from .panel import monthly_frame
 from .utils import save_plot, sharpe
 
@@ -38,6 +38,26 @@ def assign_deciles_per_date(series, n=10, device=None):
     if np.isnan(lab).any():
         return pd.Series(lab, index=series.index)
     return pd.Series(lab.astype(np.int64), index=series.index)
+
+
+def daily_portfolio_returns(daily_df, lookback_months=12, skip_months=1, n_bins=10, K=1,
+                            device=None):
+    """Daily return series of the portfolios monthly_replication forms (rule E7): the same
+    dense panel, signal and per-date labels, then Engine.daily_returns.  Returns a DataFrame
+    indexed by trading day with one column per bin (0 .. n_bins - 1) plus 'long_short' (top
+    minus bottom; NaN where either leg has no portfolio), or None where there is no signal."""
+    panel, host, dev = monthly_signal(daily_df, lookback_months, skip_months, device)
+    if host is None or np.isnan(host["M"]).all():
+        return None
+    eng = get_engine(device)
+    L, _, _, _ = eng.deciles(dev["M"], None, n_bins)
+    P, _, ms = upload_panel(panel, eng, with_volume=False)
+    mmd = int(np.diff(panel.month_start).max())
+    out = eng.daily_returns(P, ms, L, dev["NR"], n_bins=n_bins, K=K, max_month_days=mmd)
+    frame = pd.DataFrame(out.DR.cpu().numpy(), index=pd.DatetimeIndex(panel.days, name="date"),
+                         columns=list(range(n_bins)))
+    frame["long_short"] = out.DLS.cpu().numpy()
+    return frame
 
 
 @dataclass

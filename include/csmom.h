@@ -551,6 +551,51 @@ int csm_summary(csm_ctx* ctx, const double* LS, const double* TURN, const double
                 double* out);
 
 /*
+ * Daily return series of the decile and long-short portfolios (rule E7 in DESIGN.md section 7,
+ * E1 / E2 carried to the days of the holding month; no reference counterpart -- the reference
+ * stops at monthly numbers).  Label row t is held over the days d of calendar month t+1,
+ * [month_start[t+1], month_start[t+2]).  With pff[d][a] the last non-NaN price of column a in
+ * rows <= d (the ABSENT payload counts as NaN) and the base b[t][a] = pff[month_start[t+1]-1][a],
+ * a member's value relative is v[d][a] = pff[d][a] / b[t][a].  The cohort of age k (formed at
+ * t-k >= 0) and bin q takes the members of E1 -- L[t-k][a] == q, weight 1 or W[t-k][a] when that
+ * is finite and > 0, NR[t][a] not NaN -- that also have a finite base > 0; its value is
+ * C[d] = sum w v[d] / sum w, V_q[d] is the mean of C[d] over the non-empty cohorts (E2), V_q = 1
+ * on the day before the month, and DR[d][q] = V_q[d] / V_q[d-1] - 1.
+ *   P [T_d][N], month_start [T_m+1]: the daily panel of csm_month_end / csm_signal
+ *   max_month_days: an upper bound of the months' lengths in rows, <= 32
+ *   L [T_m][N] int8 labels (-1 = not ranked), NR [T_m][N] next-row returns, W nullable [T_m][N]
+ *   n_bins in {2,3,4,5,10,20,30};  1 <= K <= 12;  any N >= 1
+ *   DR [T_d][n_bins] out: NaN on the days of month 0 (no portfolio yet), on days outside
+ *     [month_start[0], month_start[T_m]) and where the month has no non-empty cohort of the bin
+ *   DLS [T_d] out: DR[d][n_bins-1] - DR[d][0], NaN if either leg is (E3's max-minus-min
+ *     fallback is not carried over)
+ *   DCNT nullable [T_m][K][n_bins] int32 out: the member counts (row T_m-1, never held, is 0)
+ *   workspace: device buffer of csm_daily_workspace(T_d, N, T_m, n_bins, K) bytes (0 for
+ *     arguments csm_daily_returns refuses)
+ * Within a month prod_d (1 + DR[d][q]) = V_q[last day]; on a panel where every cell is priced
+ * that is 1 + PR[t][q] of csm_portfolio for the same (L, NR, W, K).  Where prices are missing
+ * the monthly engine books a multi-month return at one row while this series carries the
+ * position flat until a price appears.  P is read once for any K; every sum has a fixed order,
+ * so two calls on the same inputs give the same bits.  +-inf and zero prices are out of contract.
+ */
+int64_t csm_daily_workspace(int64_t T_d, int64_t N, int32_t T_m, int32_t n_bins, int32_t K);
+int csm_daily_returns(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
+                      const int64_t* month_start, int32_t T_m, int32_t max_month_days,
+                      const int8_t* L, const double* NR, const double* W, int32_t n_bins,
+                      int32_t K, double* DR, double* DLS, int32_t* DCNT, void* workspace);
+
+/*
+ * Statistics of nS series of T entries, element i of series s at X[s + i * stride] (a column of
+ * DR: stride = n_bins; DLS: nS = 1, stride = 1).  NaN entries are dropped.  out [nS][6] = count,
+ * mean, Sharpe (src/utils.py:8-16 at `freq` periods a year, ddof = 1; NaN when the deviation is
+ * 0 or not defined), annualised volatility sd * sqrt(freq), the maximum drawdown of
+ * cumprod(1 + x) as a positive fraction of a running peak that starts at 1, and the final
+ * cumulative value.  An empty series gives count 0 and NaN elsewhere.
+ */
+int csm_series_stats(csm_ctx* ctx, const double* X, int32_t nS, int32_t T, int64_t stride,
+                     double freq, double* out);
+
+/*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
  * month-return panel R[T_m][N] (csm_momentum's R; NaN = no row).  src[B][T_m] int32 out: the
  * source months; PMb[T_m][B][N] out: month prices p0 * prod(1 + r) over the resampled months,
