@@ -188,6 +188,7 @@ __device__ __forceinline__ void scan_init(ScanLane& s, double* ring, int RS, int
 }
 
 // Consumes month m's price x of asset a; returns mom (NaN when absent / undefined).
+template <int JC = 0>   // JC > 0: J fixed at compile time (the product's ring reads unrolled)
 __device__ __forceinline__ double scan_step(ScanLane& s, double x, int m, double* ring, int RS,
                                             int W, int J, int64_t N, int64_t a,
                                             double* __restrict__ R, double* __restrict__ M,
@@ -208,9 +209,20 @@ __device__ __forceinline__ double scan_step(ScanLane& s, double x, int m, double
   s.head = (s.head + 1 == W) ? 0 : s.head + 1;
   double acc = ring[s.head * RS];
   int idx = s.head;
-  for (int k = 1; k < J; ++k) {
-    idx = (idx + 1 == W) ? 0 : idx + 1;
-    acc = acc * ring[idx * RS];
+  if constexpr (JC > 0) {
+    double f[JC];   // the ring reads all issued before the product
+#pragma unroll
+    for (int k = 1; k < JC; ++k) {
+      idx = (idx + 1 == W) ? 0 : idx + 1;
+      f[k] = ring[idx * RS];
+    }
+#pragma unroll
+    for (int k = 1; k < JC; ++k) acc = acc * f[k];
+  } else {
+    for (int k = 1; k < J; ++k) {
+      idx = (idx + 1 == W) ? 0 : idx + 1;
+      acc = acc * ring[idx * RS];
+    }
   }
   const double mom = acc - 1.0;
   const bool ranked = !isnan_d(mom);
@@ -814,6 +826,46 @@ __device__ __forceinline__ double comp(double2 v, int k) { return k == 0 ? v.x :
 // Speculative shards keep PM only for the first and last W + SHARD_PM_EDGE months (what the
 // summary walks and the repair read for a dense asset); other months are re-derived from the
 // daily panel for the rare asset that needs them (shard_pm_at).
+// The launch-level choice of "signal_tail" 2.  Where the panel has few gaps k_signal_tail reads a
+// fraction of k_signal's bytes; where a quarter of the cells have no price on the month's last
+// day its walks move about the stream's bytes in dependent trips and k_signal is 4-10 % faster
+// at C4's width.  Both kernels are launched, and every wave of both first
+// samples the same cells -- the last day row of PROBE_M months spread over the calendar at 128
+// columns spread over the panel, all loads in flight at once, cached after the first wave --
+// so all reach the same answer without sharing anything: k_signal_tail is the launch's kernel
+// where at most one sampled cell in PROBE_DEN holds no price, and the other kernel's waves
+// return.  No host round trip, no device state, the same choice for the same panel.
+#define PROBE_M 8
+#define PROBE_DEN 8
+__device__ __forceinline__ bool tail_probe(const double* __restrict__ P,
+                                           const int64_t* __restrict__ month_start, int T_m,
+                                           int64_t N, int64_t T_d) {
+  static_assert(PROBE_M == 8, "the month spacing is a shift");
+  const int lane = threadIdx.x & 63;
+  const int64_t cs = N / 128;   // column spacing (probed launches have N >= SIGNAL_BWF_MIN_N)
+  double x[PROBE_M][2];
+  bool in[PROBE_M];
+#pragma unroll
+  for (int i = 0; i < PROBE_M; ++i) {
+    const int m = (int)(((int64_t)(2 * i + 1) * T_m) >> 4);   // (/ (2 * PROBE_M))
+    const int64_t d0 = month_start[m] < 0 ? 0 : month_start[m];
+    const int64_t d1 = month_start[m + 1] < T_d ? month_start[m + 1] : T_d;
+    in[i] = d1 > d0;   // wave-uniform
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+      x[i][j] = in[i] ? P[(d1 - 1) * N + (2 * lane + j) * cs] : 0.0;
+  }
+  int gaps = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < PROBE_M; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      gaps += __popcll(__ballot(in[i] && !(x[i][j] == x[i][j])));
+      tot += in[i] ? 64 : 0;
+    }
+  return gaps * PROBE_DEN <= tot;
+}
+
 #define SHARD_PM_EDGE 8
 __device__ __forceinline__ bool shard_pm_kept(int m, int T_m, int W) {
   return m < W + SHARD_PM_EDGE || m >= T_m - (W + SHARD_PM_EDGE);
@@ -842,8 +894,11 @@ __global__ __launch_bounds__(64 * BW) void k_signal(
     const double* __restrict__ P, const int64_t* __restrict__ month_start, int T_m, int64_t N,
     int J, int skip, double* __restrict__ PMo, double* __restrict__ R, double* __restrict__ M,
     double* __restrict__ NR, const double* __restrict__ carry, const double* __restrict__ next_pm,
-    double* __restrict__ carry_out, int64_t T_d, uint16_t* __restrict__ IDS, HaloArgs ha) {
+    double* __restrict__ carry_out, int64_t T_d, uint16_t* __restrict__ IDS, HaloArgs ha,
+    int probe) {
   static_assert(!HALO || (SH && VEC == 2), "the halo prologue: shard passes, paired lanes");
+  // (launch-uniform: k_signal_tail is this panel's kernel)
+  if (probe && tail_probe(P, month_start, T_m, N, T_d)) return;
   typedef typename RowT<VEC>::T VT;
   extern __shared__ __attribute__((aligned(16))) double ring_lds[];  // [W][64 * VEC * BW]
   const int W = J + skip;
@@ -1005,14 +1060,16 @@ __global__ __launch_bounds__(64 * BW) void k_signal(
         buf[k] = *reinterpret_cast<const VT*>(&w);
       }
     } else {
+      // (a zero-length month re-loads a row of the panel too; process masks all of it)
+      const int64_t pad = nn > 0 ? nn - 1 : (f0 > 0 ? -1 : 0);
 #pragma unroll
       for (int k = 0; k < MAXD; ++k)
-        buf[k] = *reinterpret_cast<const VT*>(base + (f0 + (k < nn ? k : nn - 1)) * rstride);
+        buf[k] = *reinterpret_cast<const VT*>(base + (f0 + (k < nn ? k : pad)) * rstride);
     }
   };
   auto process = [&](const VT (&X)[MAXD], int m) {
     double pm[VEC];
-    const int nnm = BL ? (int)(month_start[m + 1] - month_start[m]) : MAXD;
+    const int nnm = (int)(month_start[m + 1] - month_start[m]);
 #pragma unroll
     for (int c = 0; c < VEC; ++c) {
       double last = 0.0;
@@ -1020,7 +1077,7 @@ __global__ __launch_bounds__(64 * BW) void k_signal(
 #pragma unroll
       for (int k = 0; k < MAXD; ++k) {
         const double x = comp(X[k], c);
-        const bool in = !BL || k < nnm;   // wave-uniform
+        const bool in = BL ? k < nnm : nnm > 0;   // wave-uniform (no row: a zero-length month)
         const bool ok = in && x == x;  // a valid price (ABSENT and missing are NaN)
         p |= in && !is_absent(x);
         v |= ok;
@@ -1114,6 +1171,192 @@ __global__ __launch_bounds__(64 * BW) void k_signal(
       }
     }
   }
+}
+
+// =====================================================================================
+// Kernel AB, tail first (the one-GPU default for even N): the month-end needs the month's last
+// valid price and whether any row is present, so a cell whose LAST day row holds a price needs
+// no other row.  Months in batches of TAIL_U; a lane loads its asset's last day row of every
+// month of the batch (one coalesced load a month, the next batch's already in flight), the
+// cells whose last row holds no price (a missing day, a listing, a delisting, an absent month)
+// are listed per wave in LDS and walked back by the wave's lanes, a cell per lane, in two lists.
+// A missing day (a NaN that is not ABSENT) loads TAIL_BACK rows before the last and almost
+// always finds its price there.  ABSENT in the last row (a listing, a delisting, an absent
+// month) is almost always a month without a price, which needs every row, so the cell loads
+// them all at once, two cells per lane and trip where the list is long; the rare missing day
+// still open after TAIL_BACK rows joins that list.  The first trips of both lists are in flight
+// together.  Then the batch's month prices are scanned from LDS.  The lists are in (month,
+// column) order, so where gaps are dense neighbouring lanes walk neighbouring columns of the
+// same rows and their requests coalesce.
+// One asset per lane: the scan is a chain of dependent LDS reads and FP64 products that nothing
+// hides once the row stream is gone, and paired lanes (k_signal's layout) give C4 782 waves for
+// 1,024 SIMDs; single lanes give twice the waves (paired: 25-60 % slower).
+// Same ring, same arithmetic as k_signal's one-asset-per-lane form: bit-identical PM / R / M /
+// NR / ids.  Every wave works alone on its 64 assets (no block barrier, no global state).
+// =====================================================================================
+#define TAIL_U 8        // months per batch
+#define TAIL_BACK 3     // day rows before the last that a cell with a missing last day loads first
+
+template <int MAXD, int BW, int JC>
+__global__ __launch_bounds__(64 * BW) void k_signal_tail(
+    const double* __restrict__ P, const int64_t* __restrict__ month_start, int T_m, int64_t N,
+    int J, int skip, double* __restrict__ PMo, double* __restrict__ R, double* __restrict__ M,
+    double* __restrict__ NR, const double* __restrict__ carry, const double* __restrict__ next_pm,
+    double* __restrict__ carry_out, int64_t T_d, uint16_t* __restrict__ IDS,
+    int probe) {
+  // (launch-uniform: k_signal is this panel's kernel)
+  if (probe && !tail_probe(P, month_start, T_m, N, T_d)) return;
+  // LDS: the ring [W][RS], the batch's month prices [TAIL_U][RS], each wave's two lists of cells
+  extern __shared__ __attribute__((aligned(16))) double ring_lds[];
+  constexpr int U = TAIL_U, RS = 64 * BW, WA = 64;
+  const int W = J + skip;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t a0 = (int64_t)blockIdx.x * RS + tid;
+  const bool live = a0 < N;
+  const int64_t as = live ? a0 : 0;
+  const int64_t aw = a0 - lane;         // the wave's first asset
+  const int64_t* ms = month_start;
+  double* hp = ring_lds + (size_t)W * RS;
+  double* hpw = hp + WA * wv;           // the wave's columns of a month row
+  uint16_t* wl = reinterpret_cast<uint16_t*>(hp + U * RS) + wv * (2 * U * WA);
+  uint16_t* wl2 = wl + U * WA;          // wl: missing last days; wl2: absent last rows
+  ScanLane sl;
+  scan_init(sl, ring_lds + tid, RS, W, carry, N, a0, live);
+  if (aw >= N) return;   // (wave-uniform; no wave waits for another)
+
+  // day rows [d0, d1) of month m, inside the panel
+  auto month_rows = [&](int m, int64_t& d0, int64_t& d1) {
+    d0 = ms[m];
+    d1 = ms[m + 1];
+    d0 = d0 < 0 ? 0 : d0;
+    d1 = d1 < T_d ? d1 : T_d;
+  };
+  auto load_last = [&](double (&xl)[U], int m0) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      xl[u] = absent_val();
+      if (m0 + u < T_m) {   // (block-uniform)
+        int64_t d0, d1;
+        month_rows(m0 + u, d0, d1);
+        if (d1 > d0) xl[u] = P[(d1 - 1) * N + as];
+      }
+    }
+  };
+  // one more row of a listed cell, walking back: the latest valid price, and presence
+  auto fold = [&](double y, double& x, bool& got, bool& p) {
+    if (!got && y == y) { x = y; got = true; }
+    p |= !is_absent(y);
+  };
+  // A trip of a walk: 64 listed cells, a cell per lane.  issue() puts the cell's KK rows before
+  // its last in flight, finish_*() folds them into the month price.
+  constexpr int K = MAXD - 1;
+  struct Walk {
+    int item, u, col;
+    int64_t d0, d1;
+    bool act;
+  };
+  auto issue = [&](auto& xs, Walk& w, const uint16_t* list, int it, int n, int m0) {
+    constexpr int KK = sizeof(xs) / sizeof(double);
+    w.act = it < n;
+    w.item = w.act ? (int)list[it] : 0;
+    w.u = w.item / WA;     // the batch's month
+    w.col = w.item % WA;   // the wave's column
+    month_rows(m0 + w.u, w.d0, w.d1);
+    const int64_t a = aw + w.col;
+#pragma unroll
+    for (int k = 0; k < KK; ++k) {
+      const int64_t d = w.d1 - 2 - k;
+      xs[k] = (w.act && d >= w.d0) ? P[d * N + a] : absent_val();
+    }
+  };
+  // a missing last day: the price TAIL_BACK rows back, or on to the list of whole months
+  auto finish_back = [&](const double (&xs)[TAIL_BACK], const Walk& w, int& nb) {
+    bool p = true, got = false;   // (a last row that is not ABSENT is a present row)
+    double x = 0.0;
+#pragma unroll
+    for (int k = 0; k < TAIL_BACK; ++k) fold(xs[k], x, got, p);
+    const bool more = w.act && !got && w.d1 - 2 - TAIL_BACK >= w.d0;
+    if (w.act && !more) hpw[w.u * RS + w.col] = got ? x : qnan();
+    const uint64_t mk = __ballot(more);
+    if (more) wl2[nb + lane_prefix(mk)] = (uint16_t)w.item;
+    nb += __popcll(mk);
+  };
+  auto finish_month = [&](const double (&xs)[K], const Walk& w) {
+    bool p = !is_absent(hpw[w.u * RS + w.col]), got = false;
+    double x = 0.0;
+#pragma unroll
+    for (int k = 0; k < K; ++k) fold(xs[k], x, got, p);
+    if (w.act) hpw[w.u * RS + w.col] = got ? x : (p ? qnan() : absent_val());
+  };
+  // up to 128 cells of the whole-month list from index i0: both halves' rows in flight at once
+  auto walk_months = [&](int i0, int n, int m0) {
+    double XS[K], XT[K];
+    Walk wb, wc;
+    const bool two = i0 + 64 < n;   // wave-uniform
+    issue(XS, wb, wl2, i0 + lane, n, m0);
+    if (two) issue(XT, wc, wl2, i0 + 64 + lane, n, m0);
+    finish_month(XS, wb);
+    if (two) finish_month(XT, wc);
+  };
+
+  double xa[U], xb[U];
+  load_last(xa, 0);
+  for (int m0 = 0; m0 < T_m; m0 += U) {
+    load_last(xb, m0 + U);
+    int na = 0, nb = 0;   // wave-uniform: the listed missing days, the listed absent last rows
+    // ---- the batch's last rows into LDS, the cells without a price listed ----
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      hp[u * RS + tid] = xa[u];
+      bool in = false;
+      if (m0 + u < T_m) {
+        int64_t d0, d1;
+        month_rows(m0 + u, d0, d1);
+        in = d1 > d0;   // (a zero-length month is ABSENT: nothing to walk)
+      }
+      const double x = xa[u];
+      const bool need = live && in && !(x == x);
+      const bool nb_ = need && is_absent(x), na_ = need && !nb_;
+      const uint64_t mka = __ballot(na_), mkb = __ballot(nb_);
+      const int item = u * WA + lane;
+      if (na_) wl[na + lane_prefix(mka)] = (uint16_t)item;
+      if (nb_) wl2[nb + lane_prefix(mkb)] = (uint16_t)item;
+      na += __popcll(mka);
+      nb += __popcll(mkb);
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- the walks, a cell per lane ----
+    if (na + nb > 0) {
+      double xs[TAIL_BACK];
+      Walk wa;
+      int db = nb < 128 ? nb : 128;   // whole months walked so far (the back walks append more)
+      issue(xs, wa, wl, lane, na, m0);
+      walk_months(0, db, m0);
+      finish_back(xs, wa, nb);
+      for (int it0 = 64; it0 < na; it0 += 64) {
+        issue(xs, wa, wl, it0 + lane, na, m0);
+        finish_back(xs, wa, nb);
+      }
+      __builtin_amdgcn_wave_barrier();
+      for (; db < nb; db += 128) walk_months(db, nb, m0);
+    }
+    __builtin_amdgcn_wave_barrier();
+    // ---- the scan of the batch's month prices (k_signal's process() from pm on) ----
+#pragma unroll 1
+    for (int u = 0; u < U; ++u) {
+      const int m = m0 + u;
+      if (m >= T_m) break;
+      if (!live) continue;
+      const double pm = hp[u * RS + tid];   // (the walks wrote the canonical NaN / ABSENT)
+      if (PMo) PMo[(int64_t)m * N + a0] = pm;
+      const double mom = scan_step<JC>(sl, pm, m, ring_lds + tid, RS, W, J, N, a0, R, M, NR);
+      if (IDS) IDS[(int64_t)m * N + a0] = (uint16_t)csm_fid(mom);
+    }
+    __builtin_amdgcn_wave_barrier();   // (the batch's LDS is the next batch's)
+#pragma unroll
+    for (int u = 0; u < U; ++u) xa[u] = xb[u];
+  }
+  if (live) scan_finish(sl, ring_lds + tid, RS, W, N, a0, NR, next_pm, carry_out);
 }
 
 // =====================================================================================
@@ -2519,6 +2762,11 @@ __global__ __launch_bounds__(UNION_THREADS) void k_shard_union(const uint64_t* _
 // lost their A/B (profiles/r0*/experiments) are not in the library.
 static int g_tune_signal_vec = 2;      // k_signal assets per lane: 2 (paired 16-B rows) | 1 (odd N)
 static int g_tune_signal_bwf = 0;      // k_signal blocks: 0 auto | 1 one wave | 4 four barrier-free waves x 2 month buffers (buffer loads)
+// the one-GPU fused signal (even N, aligned buffers): 0 k_signal, every day row streamed | 1
+// k_signal_tail, last day rows and walks | 2 (auto) k_signal_tail below SIGNAL_BWF_MIN_N assets;
+// from there on both are launched and each samples the panel's last day rows (tail_probe):
+// k_signal_tail runs where at most 1 sampled cell in 8 holds no price, k_signal elsewhere
+static int g_tune_signal_tail = 2;
 static int g_tune_signal_j12 = 1;      // wide shard k_signal: J = 12 with its product length fixed at compile time (0: runtime J)
 static int g_tune_cols_wg = 1;          // halo pass's listed columns: one workgroup per column (month prices into LDS) | 0 one thread per column
 #define SIGNAL_BWF_MIN_N (180 * 512)   // auto: 4-wave blocks once the grid still covers >= 180 CUs
@@ -2551,6 +2799,7 @@ static const TuneKnob g_knobs[] = {
     {"signal_vec", &g_tune_signal_vec, [](int v) { return v == 1 || v == 2; }},
     {"signal_bwf", &g_tune_signal_bwf, [](int v) { return v == 0 || v == 1 || v == 4; }},
     {"signal_j12", &g_tune_signal_j12, [](int v) { return v == 0 || v == 1; }},
+    {"signal_tail", &g_tune_signal_tail, [](int v) { return v >= 0 && v <= 2; }},
     {"cols_wg", &g_tune_cols_wg, [](int v) { return v == 0 || v == 1; }},
     {"dec_merge", &g_tune_dec_merge, [](int v) { return v == 0 || v == 1; }},
     {"mj_reg", &g_tune_mj_reg, [](int v) { return v >= 0 && v <= 2; }},
@@ -2780,10 +3029,41 @@ static int signal_launch(csm_ctx* ctx, const char* who, const double* P, int64_t
     return set_err(ctx, CSM_E_INVAL, "%s: months longer than 32 days are not supported "
                    "(use csm_month_end + csm_momentum)", who);
   if (T_m == 0) return CSM_OK;
+  if (T_d == 0)
+    return set_err(ctx, CSM_E_INVAL, "%s: %d months and no day row", who, T_m);
   const int W = J + skip;
   const bool can2 = (N % 2 == 0) && aligned16(P) && (!PM || aligned16(PM)) && aligned16(M) &&
                     aligned16(NR) && (!R || aligned16(R));
   const int vec = (g_tune_signal_vec == 1 || !can2) ? 1 : 2;
+  // Tail first (k_signal_tail): the whole-panel pass on even N and aligned buffers, two
+  // independent waves of 64 assets per block; ring, batch and lists in LDS (the CU's 160 KiB
+  // bound J + skip).  J = 12 with its product length fixed at compile time: the scan's chain
+  // is this kernel's critical path.  signal_tail 2: both kernels launched, tail_probe's choice
+  // made by each.
+  const size_t tlds = (size_t)(W + TAIL_U) * 128 * sizeof(double) + (size_t)2 * TAIL_U * 128 * sizeof(uint16_t);
+  // (auto below SIGNAL_BWF_MIN_N: k_signal is one wave per 128 assets there, its time set by the
+  // 461-month chain whatever N, and k_signal_tail measured 0.55-0.65 x even on the gap-heavy
+  // panel at 32,768 and 65,536 assets: no probe)
+  int tail = (!sh && !halo && can2 && tlds <= 160 * 1024) ? g_tune_signal_tail : 0;
+  if (tail == 2 && N < (int64_t)SIGNAL_BWF_MIN_N) tail = 1;
+  int probe_ = tail == 2;
+  if (tail != 0) {
+    const bool d23 = max_month_days <= 23, j12 = J == 12;
+    const void* fn =
+        d23 ? (j12 ? (const void*)k_signal_tail<23, 2, 12> : (const void*)k_signal_tail<23, 2, 0>)
+            : (j12 ? (const void*)k_signal_tail<32, 2, 12> : (const void*)k_signal_tail<32, 2, 0>);
+    if (tlds > 65536)
+      HIP_CHECK(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tlds));
+    const unsigned blocks = (unsigned)((N + 127) / 128);
+    int T_m_ = T_m, J_ = J, skip_ = skip;
+    int64_t N_ = N, T_d_ = T_d;
+    void* args[] = {(void*)&P, (void*)&month_start, &T_m_, &N_, &J_, &skip_, (void*)&PM, (void*)&R,
+                    (void*)&M, (void*)&NR, (void*)&carry, (void*)&next_pm, (void*)&carry_out, &T_d_,
+                    (void*)&ids, &probe_};
+    HIP_CHECK(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(128), args, tlds, ctx->stream));
+    LAUNCH_CHECK(ctx, who);
+    if (tail == 1) return CSM_OK;
+  }
   // Barrier-free 4-wave blocks (adjacent 1-KiB column slices walked independently, 2 month
   // buffers, raw buffer loads with the padding rows out of range): the wide-panel default
   // (C4 1.75-1.85 -> 1.63-1.78 ms, then buffer loads 1.695 -> 1.674, profiles/r02/experiments).
@@ -2831,7 +3111,7 @@ static int signal_launch(csm_ctx* ctx, const char* who, const double* P, int64_t
     HaloArgs ha = halo ? *halo : HaloArgs{0, 0, 0, 0, nullptr};
     void* args[] = {(void*)&P, (void*)&month_start, &T_m_, &N_, &J_, &skip_, (void*)&PM, (void*)&R,
                     (void*)&M, (void*)&NR, (void*)&carry, (void*)&next_pm, (void*)&carry_out, &T_d_,
-                    (void*)&ids, (void*)&ha};
+                    (void*)&ids, (void*)&ha, &probe_};
     HIP_CHECK(ctx, hipLaunchKernel(fn, dim3(blocks), dim3(64 * bw), args, lds, ctx->stream));
   }
   LAUNCH_CHECK(ctx, who);

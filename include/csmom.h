@@ -45,7 +45,15 @@ int csm_abi_version(void);
  * drive the fallbacks on inputs that would not reach them): "signal_vec" (2 paired 16-B rows |
  * 1 one asset per lane, the odd-N path), "signal_bwf" (0 auto | 1 one-wave blocks | 4 the wide
  * panels' four barrier-free waves with buffer loads), "signal_j12" (1 the wide date-shard kernel's
- * J = 12 with the product length fixed at compile time | 0 runtime J), "cols_wg" (1 the halo pass's listed
+ * J = 12 with the product length fixed at compile time | 0 runtime J), "signal_tail" (the
+ * one-GPU fused signal on even N and 16-B aligned buffers: 0 the streaming kernel, every day row
+ * read | 1 the tail-first kernel -- each month's last day row, then a walk back, a cell per
+ * lane, only where that row holds no price | 2 auto, the default: the tail-first kernel below
+ * 92,160 assets; from there on both kernels are launched and every wave of both first samples
+ * the same 1,024 last-day cells over the calendar and the panel: the tail-first kernel runs
+ * where at most one sampled cell in eight holds no price, the streaming kernel elsewhere, and
+ * the other returns at once -- no host round trip, no state on the device or between calls),
+ * "cols_wg" (1 the halo pass's listed
  * columns summarised / repaired one workgroup per column, month prices derived together in LDS |
  * 0 one thread per column), "dec_merge" (1 the merged decile sweep on
  * ids, the general kernel for the rows it leaves | 0 the general kernel only), "dec_split" (2

@@ -75,6 +75,27 @@ def read_counter(d, counter):
     return {k: list(v.values()) for k, v in vals.items()}
 
 
+# bench.py looks a stage's kernel up by the name it has always had ("k_signal", or an
+# instantiation "k_signal<...>"); a kernel that took that stage over under another name is also
+# entered under the old one, marked as an alias, so the bench line's `traffic` / `profile_frac`
+# are the bytes and time of the kernel that actually ran.
+ALIASES = {"k_signal": "k_signal_tail"}
+
+
+def add_aliases(kern):
+    for old, new in ALIASES.items():
+        ks = [k for k in kern if k == new or k.startswith(new + "<")]
+        if not ks:
+            continue
+        top = max(ks, key=lambda k: kern[k].get("total_ns", 0.0))
+        # (an auto launch also enqueues the old kernel, whose blocks return after the probe: the
+        # alias goes in only where the new kernel did the stage's work, and bench.py's lookup
+        # takes the entry with the most device time)
+        olds = [kern[k].get("total_ns", 0.0) for k in kern if k == old or k.startswith(old + "<")]
+        if kern[top].get("total_ns", 0.0) > max(olds, default=0.0):
+            kern[old] = dict(kern[top], alias_of=top)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("prof_dir")
@@ -104,6 +125,7 @@ def main():
                      hbm_bytes_per_launch=2.0 * f_kb * 1024.0 + w_kb * 1024.0,
                      pmc_dispatches=max(len(fv), len(wv)))
         kern[k] = e
+    add_aliases(kern)
     lib = os.path.join(PKG, "libcsmom.so")
     out = {"config": a.config, "workload": a.workload, "N": a.N, "T_d": a.T_d,
            "git_head": a.git_head, "host": socket.gethostname(),
