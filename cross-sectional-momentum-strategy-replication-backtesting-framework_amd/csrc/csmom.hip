@@ -22,6 +22,7 @@
 
 
 #include "csm_common.h"
+#include "scan.h"
 
 // =====================================================================================
 // Kernel A: month-end aggregation.  One thread per (month, VEC assets); a wave streams
@@ -159,92 +160,23 @@ __global__ __launch_bounds__(256) void k_month_end(const double* __restrict__ P,
 }
 
 // =====================================================================================
-// Per-asset scan state and one present-row step (shared by k_momentum and k_signal).
-// The J+skip ring of factors fl(1+ret) lives in LDS, slot-major with a per-lane column
-// (stride RS doubles), so a wave's ring accesses are conflict-free.
-// mom = (prod over the J oldest ring entries of fl(1+ret), left to right) - 1.
+// The month step's sites with an LDS ring (shared by k_momentum and k_signal): scan.h's
+// scan_step_on with the LDS ring policy, and its form for two adjacent assets.
 // =====================================================================================
-struct ScanLane {
-  double pff;   // last valid month price (features.py:44 grouped ffill)
-  double psff;  // last valid price among ranked rows (run_demo.py:48 subset ffill)
-  int head;     // index of the oldest ring entry
-  int prev;     // month of the pending ranked row (its next_ret waits for the next row)
-};
-
-__device__ __forceinline__ void scan_init(ScanLane& s, double* ring, int RS, int W,
-                                          const double* __restrict__ carry, int64_t N,
-                                          int64_t a, bool live) {
-  if (live && carry) {
-    for (int k = 0; k < W; ++k) ring[k * RS] = carry[(int64_t)k * N + a];
-    s.pff = carry[(int64_t)W * N + a];
-    s.psff = carry[(int64_t)(W + 1) * N + a];
-  } else {
-    for (int k = 0; k < W; ++k) ring[k * RS] = qnan();
-    s.pff = qnan();
-    s.psff = qnan();
-  }
-  s.head = 0;
-  s.prev = -1;
-}
-
-// Consumes month m's price x of asset a; returns mom (NaN when absent / undefined).
-template <int JC = 0>   // JC > 0: J fixed at compile time (the product's ring reads unrolled)
+template <int JC = 0>
 __device__ __forceinline__ double scan_step(ScanLane& s, double x, int m, double* ring, int RS,
                                             int W, int J, int64_t N, int64_t a,
                                             double* __restrict__ R, double* __restrict__ M,
                                             double* __restrict__ NR) {
-  const double NaN = qnan();
-  const int64_t o = (int64_t)m * N + a;
-  if (is_absent(x)) {
-    if (R) R[o] = NaN;
-    M[o] = NaN;
-    NR[o] = NaN;
-    return NaN;
-  }
-  const bool xv = !isnan_d(x);
-  const double pnew = xv ? x : s.pff;
-  const double ret = pnew / s.pff - 1.0;
-  s.pff = pnew;
-  ring[s.head * RS] = 1.0 + ret;          // push: overwrite the oldest, advance head
-  s.head = (s.head + 1 == W) ? 0 : s.head + 1;
-  double acc = ring[s.head * RS];
-  int idx = s.head;
-  if constexpr (JC > 0) {
-    double f[JC];   // the ring reads all issued before the product
-#pragma unroll
-    for (int k = 1; k < JC; ++k) {
-      idx = (idx + 1 == W) ? 0 : idx + 1;
-      f[k] = ring[idx * RS];
-    }
-#pragma unroll
-    for (int k = 1; k < JC; ++k) acc = acc * f[k];
-  } else {
-    for (int k = 1; k < J; ++k) {
-      idx = (idx + 1 == W) ? 0 : idx + 1;
-      acc = acc * ring[idx * RS];
-    }
-  }
-  const double mom = acc - 1.0;
-  const bool ranked = !isnan_d(mom);
-  const double ps_new = xv ? x : s.psff;
-  if (s.prev >= 0) NR[(int64_t)s.prev * N + a] = ps_new / s.psff - 1.0;
-  if (ranked) {
-    s.psff = ps_new;
-    s.prev = m;
-  } else {
-    NR[o] = NaN;
-    s.prev = -1;
-  }
-  if (R) R[o] = ret;
-  M[o] = mom;
-  return mom;
+  return scan_step_on(s, x, m, N, a, R, M, NR,
+                      [&](double fct) { return lds_push_mom<JC>(s, ring, RS, W, J, fct); });
 }
 
 // scan_step for two adjacent assets a0, a0 + 1 (a0 even) with their stores paired: mom_J
 // (and ret_1m) as one 16-B store per row, next_ret as one 16-B store when both assets write
 // the same row (the steady state), so a wave issues half the store instructions.  Same
 // arithmetic in the same order as two scan_step calls: bit-identical outputs.
-template <int JC = 0>   // JC > 0: J fixed at compile time (the product's ring reads unrolled)
+template <int JC = 0>
 __device__ __forceinline__ void scan_step_pair(ScanLane (&s)[2], const double (&x)[2], int m,
                                                double* ring0, int RS, int W, int J, int64_t N,
                                                int64_t a0, double* __restrict__ R,
@@ -257,40 +189,20 @@ __device__ __forceinline__ void scan_step_pair(ScanLane (&s)[2], const double (&
   bool wc[2];         // NaN next_ret at row m
 #pragma unroll
   for (int c = 0; c < 2; ++c) {
-    double* ring = ring0 + c;
     wp[c] = -1;
     vp[c] = NaN;
     if (is_absent(x[c])) {
       ret[c] = NaN; mom[c] = NaN; wc[c] = true;
       continue;
     }
-    const bool xv = !isnan_d(x[c]);
-    const double pnew = xv ? x[c] : s[c].pff;
-    ret[c] = pnew / s[c].pff - 1.0;
-    s[c].pff = pnew;
-    ring[s[c].head * RS] = 1.0 + ret[c];
-    s[c].head = (s[c].head + 1 == W) ? 0 : s[c].head + 1;
-    double acc = ring[s[c].head * RS];
-    int idx = s[c].head;
-    if constexpr (JC > 0) {
-      double f[JC];   // the ring reads all issued before the product
-#pragma unroll
-      for (int k = 1; k < JC; ++k) {
-        idx = (idx + 1 == W) ? 0 : idx + 1;
-        f[k] = ring[idx * RS];
-      }
-#pragma unroll
-      for (int k = 1; k < JC; ++k) acc = acc * f[k];
-    } else {
-      for (int k = 1; k < J; ++k) {
-        idx = (idx + 1 == W) ? 0 : idx + 1;
-        acc = acc * ring[idx * RS];
-      }
-    }
-    mom[c] = acc - 1.0;
+    ret[c] = price_step(x[c], s[c].pff);
+    mom[c] = lds_push_mom<JC>(s[c], ring0 + c, RS, W, J, 1.0 + ret[c]);
+    // rank_step's update restated at the site (its arithmetic, ffill and subset_ret, is shared):
+    // through any function form the 512-VGPR one-wave k_signal variants spill more than they do
+    // with these statements inline
     const bool ranked = !isnan_d(mom[c]);
-    const double ps_new = xv ? x[c] : s[c].psff;
-    if (s[c].prev >= 0) { wp[c] = s[c].prev; vp[c] = ps_new / s[c].psff - 1.0; }
+    const double ps_new = ffill(x[c], s[c].psff);
+    if (s[c].prev >= 0) { wp[c] = s[c].prev; vp[c] = subset_ret(ps_new, s[c].psff); }
     if (ranked) {
       s[c].psff = ps_new;
       s[c].prev = m;
@@ -301,54 +213,9 @@ __device__ __forceinline__ void scan_step_pair(ScanLane (&s)[2], const double (&
     }
   }
   const int64_t o = (int64_t)m * N + a0;
-  if (R) *reinterpret_cast<double2*>(R + o) = make_double2(ret[0], ret[1]);
-  *reinterpret_cast<double2*>(M + o) = make_double2(mom[0], mom[1]);
-  if (wp[0] >= 0 && wp[0] == wp[1]) {
-    *reinterpret_cast<double2*>(NR + (int64_t)wp[0] * N + a0) = make_double2(vp[0], vp[1]);
-  } else {
-    if (wp[0] >= 0) NR[(int64_t)wp[0] * N + a0] = vp[0];
-    if (wp[1] >= 0) NR[(int64_t)wp[1] * N + a0 + 1] = vp[1];
-  }
-  if (wc[0] && wc[1]) {
-    *reinterpret_cast<double2*>(NR + o) = make_double2(NaN, NaN);
-  } else {
-    if (wc[0]) NR[o] = NaN;
-    if (wc[1]) NR[o + 1] = NaN;
-  }
-}
-
-__device__ __forceinline__ void scan_finish(ScanLane& s, double* ring, int RS, int W, int64_t N,
-                                            int64_t a, double* __restrict__ NR,
-                                            const double* __restrict__ next_pm,
-                                            double* __restrict__ carry_out) {
-  if (s.prev >= 0) {
-    double nr = qnan();
-    if (next_pm) {
-      const double x = next_pm[a];
-      if (!is_absent(x)) {
-        const double ps_new = isnan_d(x) ? s.psff : x;
-        nr = ps_new / s.psff - 1.0;
-      }
-    }
-    NR[(int64_t)s.prev * N + a] = nr;
-  }
-  if (carry_out) {
-    int idx = s.head;
-    for (int k = 0; k < W; ++k) {  // carry rows hold the ring's factors, oldest first
-      carry_out[(int64_t)k * N + a] = ring[idx * RS];
-      idx = (idx + 1 == W) ? 0 : idx + 1;
-    }
-    carry_out[(int64_t)W * N + a] = s.pff;
-    carry_out[(int64_t)(W + 1) * N + a] = s.psff;
-  }
-}
-
-// Month range of chunk g when T_m months are split into G contiguous chunks (earlier
-// chunks take the remainder) -- the same split as distributed.month_partition.
-__device__ __forceinline__ void chunk_range(int T_m, int G, int g, int& m0, int& m1) {
-  const int base = T_m / G, rem = T_m % G;
-  m0 = g * base + (g < rem ? g : rem);
-  m1 = m0 + base + (g < rem ? 1 : 0);
+  if (R) store_pair(R + o, ret[0], ret[1]);
+  store_pair(M + o, mom[0], mom[1]);
+  store_next_ret_pair(NR, N, a0, o, wp, vp, wc);
 }
 
 // =====================================================================================
@@ -471,33 +338,19 @@ __global__ __launch_bounds__(256) void k_momentum_multi(const double* __restrict
           }
         continue;
       }
-      const bool xv = !isnan_d(x);
-      const double pnew = xv ? x : pff;
-      const double ret = pnew / pff - 1.0;
-      pff = pnew;
-      ring[head * RS] = 1.0 + ret;          // push: overwrite the oldest, advance head
-      head = (head + 1 == W) ? 0 : head + 1;
+      const double ret = price_step(x, pff);
+      lds_push(ring, RS, W, head, 1.0 + ret);
 #pragma unroll
       for (int q = 0; q < MJ_MAX; ++q) {
         if (q >= nJ) break;
         const int J = mj.J[q];
         int idx = head + (W - J - skip);      // oldest of this J's window
         if (idx >= W) idx -= W;
-        double acc = ring[idx * RS];
-        for (int k = 1; k < J; ++k) {
-          idx = (idx + 1 == W) ? 0 : idx + 1;
-          acc = acc * ring[idx * RS];
-        }
-        const double mom = acc - 1.0;
-        const double ps_new = xv ? x : psff[q];
-        if (prev[q] >= 0) mj.NR[q][(int64_t)prev[q] * N + a] = ps_new / psff[q] - 1.0;
-        if (!isnan_d(mom)) {
-          psff[q] = ps_new;
-          prev[q] = m;
-        } else {
-          mj.NR[q][o] = NaN;
-          prev[q] = -1;
-        }
+        const double mom = lds_prod(ring, RS, W, J, idx) - 1.0;
+        double* NRq = mj.NR[q];
+        if (rank_step(x, mom, m, psff[q], prev[q],
+                      [&](int row, double nr) { NRq[(int64_t)row * N + a] = nr; }))
+          NRq[o] = NaN;
         mj.M[q][o] = mom;
         if (mj.IDS[q]) mj.IDS[q][o] = (uint16_t)csm_fid(mom);
       }
@@ -551,29 +404,16 @@ __global__ __launch_bounds__(256) void k_momentum_multi_reg(const double* __rest
           }
         continue;
       }
-      const bool xv = !isnan_d(x);
-      const double pnew = xv ? x : pff;
-      const double ret = pnew / pff - 1.0;
-      pff = pnew;
-#pragma unroll
-      for (int k = 0; k + 1 < RW; ++k) f[k] = f[k + 1];
-      f[RW - 1] = 1.0 + ret;
+      const double ret = price_step(x, pff);
+      reg_push(f, 1.0 + ret);
 #pragma unroll
       for (int q = 0; q < MJ_MAX; ++q) {
         if (q >= nJ) break;
-        double acc = 1.0;
-#pragma unroll
-        for (int k = 0; k < RW; ++k) acc = (k >= lo[q] && k < hi) ? acc * f[k] : acc;
-        const double mom = acc - 1.0;
-        const double ps_new = xv ? x : psff[q];
-        if (prev[q] >= 0) mj.NR[q][(int64_t)prev[q] * N + a] = ps_new / psff[q] - 1.0;
-        if (!isnan_d(mom)) {
-          psff[q] = ps_new;
-          prev[q] = m;
-        } else {
-          mj.NR[q][o] = NaN;
-          prev[q] = -1;
-        }
+        const double mom = mj_window<RW, false>(f, q, lo[q], hi) - 1.0;
+        double* NRq = mj.NR[q];
+        if (rank_step(x, mom, m, psff[q], prev[q],
+                      [&](int row, double nr) { NRq[(int64_t)row * N + a] = nr; }))
+          NRq[o] = NaN;
         mj.M[q][o] = mom;
         if (mj.IDS[q]) mj.IDS[q][o] = (uint16_t)csm_fid(mom);
       }
@@ -596,29 +436,9 @@ __global__ __launch_bounds__(256) void k_momentum_multi_reg(const double* __rest
 // FIX: the default grid J = 3, 6, 9, 12 (in that order), skip 1, in a 13-slot ring with
 // compile-time windows (J - 1 multiplies each, no predicated slots): the same oldest-first
 // product (1.0 * x == x), about half the code -- the predicated chunked kernel was 85 KB, past
-// the instruction cache.
-template <int RW, bool FIX>
-__device__ __forceinline__ double mj_window(const double (&f)[RW], int q, int lo, int hi) {
-  if constexpr (FIX) {
-    constexpr int Jq[4] = {3, 6, 9, 12};
-    double acc = 0.0;
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      if (qq != q) continue;
-      const int l = RW - Jq[qq] - 1;
-      double a = f[l];
-#pragma unroll
-      for (int k = l + 1; k < RW - 1; ++k) a = a * f[k];
-      acc = a;
-    }
-    return acc;
-  }
-  double acc = 1.0;
-#pragma unroll
-  for (int k = 0; k < RW; ++k) acc = (k >= lo && k < hi) ? acc * f[k] : acc;
-  return acc;
-}
-
+// the instruction cache (mj_window).
+// The step's pieces run on every row with the state kept by selects on the absent predicate,
+// not a branch: an absent row's x is a NaN, so price_step leaves pff as it is by itself.
 template <int RW, bool CH = false, bool FIX = false>
 __global__ __launch_bounds__(256) void k_momentum_multi_reg2(const double* __restrict__ PM,
                                                              int T_m, int64_t N, int nJ, int skip,
@@ -683,15 +503,13 @@ __global__ __launch_bounds__(256) void k_momentum_multi_reg2(const double* __res
       if (m >= me) break;
       const double xs[2] = {buf[j].x, buf[j].y};
       const int64_t o = (int64_t)m * N + a0;
-      bool ab[2], xv[2];
+      bool ab[2];
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
-        const double x = xs[c];
-        ab[c] = is_absent(x);
-        xv[c] = x == x;
-        const double pnew = xv[c] ? x : pff[c];
-        const double ret = pnew / pff[c] - 1.0;
-        pff[c] = ab[c] ? pff[c] : pnew;
+        ab[c] = is_absent(xs[c]);
+        const double ret = price_step(xs[c], pff[c]);   // (an absent x is a NaN: pff stays)
+        // reg_push restated with selects on the absent predicate (through the shared function the
+        // chunked FIX instantiation grows 4 % and C3's scan stage 3 %)
 #pragma unroll
         for (int k = 0; k + 1 < RW; ++k) f[c][k] = ab[c] ? f[c][k] : f[c][k + 1];
         f[c][RW - 1] = ab[c] ? f[c][RW - 1] : 1.0 + ret;
@@ -706,29 +524,17 @@ __global__ __launch_bounds__(256) void k_momentum_multi_reg2(const double* __res
         for (int c = 0; c < 2; ++c) {
           const double acc = mj_window<RW, FIX>(f[c], q, lo[q], hi);
           mom[c] = ab[c] ? NaN : acc - 1.0;
-          const double ps_new = xv[c] ? xs[c] : psff[c][q];
+          // rank_step restated with selects on the absent predicate (no branch in this kernel)
+          const double ps_new = ffill(xs[c], psff[c][q]);
           wp[c] = (!ab[c] && prev[c][q] >= 0) ? prev[c][q] : -1;
-          vp[c] = ps_new / psff[c][q] - 1.0;
+          vp[c] = subset_ret(ps_new, psff[c][q]);
           const bool ranked = mom[c] == mom[c];
           wc[c] = !ranked;
           psff[c][q] = ranked ? ps_new : psff[c][q];
           prev[c][q] = ranked ? m : (ab[c] ? prev[c][q] : -1);
         }
-        double* Mq = mj.M[q];
-        double* NRq = mj.NR[q];
-        *reinterpret_cast<double2*>(Mq + o) = make_double2(mom[0], mom[1]);
-        if (wp[0] >= 0 && wp[0] == wp[1]) {
-          *reinterpret_cast<double2*>(NRq + (int64_t)wp[0] * N + a0) = make_double2(vp[0], vp[1]);
-        } else {
-          if (wp[0] >= 0) NRq[(int64_t)wp[0] * N + a0] = vp[0];
-          if (wp[1] >= 0) NRq[(int64_t)wp[1] * N + a0 + 1] = vp[1];
-        }
-        if (wc[0] && wc[1]) {
-          *reinterpret_cast<double2*>(NRq + o) = make_double2(NaN, NaN);
-        } else {
-          if (wc[0]) NRq[o] = NaN;
-          if (wc[1]) NRq[o + 1] = NaN;
-        }
+        store_pair(mj.M[q] + o, mom[0], mom[1]);
+        store_next_ret_pair(mj.NR[q], N, a0, o, wp, vp, wc);
         if (mj.IDS[q])
           *reinterpret_cast<uint32_t*>(mj.IDS[q] + o) = csm_fid(mom[0]) | (csm_fid(mom[1]) << 16);
       }
@@ -740,14 +546,8 @@ __global__ __launch_bounds__(256) void k_momentum_multi_reg2(const double* __res
     const double x = CH ? npm[(int64_t)g * N + a0 + c] : absent_val();
 #pragma unroll
     for (int q = 0; q < MJ_MAX; ++q)
-      if (q < nJ && prev[c][q] >= 0) {
-        double nr = NaN;
-        if (CH && !is_absent(x)) {
-          const double ps_new = isnan_d(x) ? psff[c][q] : x;
-          nr = ps_new / psff[c][q] - 1.0;
-        }
-        mj.NR[q][(int64_t)prev[c][q] * N + a0 + c] = nr;
-      }
+      if (q < nJ && prev[c][q] >= 0)
+        mj.NR[q][(int64_t)prev[c][q] * N + a0 + c] = pending_finish(x, psff[c][q]);
   }
 }
 
@@ -757,25 +557,9 @@ __global__ __launch_bounds__(256) void k_momentum_multi_reg2(const double* __res
 __device__ __forceinline__ void scan_shadow(ScanLane& s, double x, int m, double* ring, int RS,
                                             int W, int J) {
   if (is_absent(x)) return;
-  const bool xv = !isnan_d(x);
-  const double pnew = xv ? x : s.pff;
-  const double ret = pnew / s.pff - 1.0;
-  s.pff = pnew;
-  ring[s.head * RS] = 1.0 + ret;
-  s.head = (s.head + 1 == W) ? 0 : s.head + 1;
-  double acc = ring[s.head * RS];
-  int idx = s.head;
-  for (int k = 1; k < J; ++k) {
-    idx = (idx + 1 == W) ? 0 : idx + 1;
-    acc = acc * ring[idx * RS];
-  }
-  const bool ranked = !isnan_d(acc - 1.0);
-  if (ranked) {
-    s.psff = xv ? x : s.psff;
-    s.prev = m;
-  } else {
-    s.prev = -1;
-  }
+  const double ret = price_step(x, s.pff);
+  const double mom = lds_push_mom(s, ring, RS, W, J, 1.0 + ret);
+  rank_step(x, mom, m, s.psff, s.prev, [](int, double) {});
 }
 
 #define HALO_WALK 24   // a business month's day rows in one batch of loads
@@ -1148,15 +932,8 @@ __global__ __launch_bounds__(64 * BW) void k_signal(
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       if constexpr (HALO) {   // scan_finish's pending row, with the prologue's forward price
-        if (sl[k].prev >= 0) {
-          double nr = qnan();
-          const double x = npmh[k];
-          if (!is_absent(x)) {
-            const double ps_new = isnan_d(x) ? sl[k].psff : x;
-            nr = ps_new / sl[k].psff - 1.0;
-          }
-          NR[(int64_t)sl[k].prev * N + a0 + k] = nr;
-        }
+        if (sl[k].prev >= 0)
+          NR[(int64_t)sl[k].prev * N + a0 + k] = pending_finish(npmh[k], sl[k].psff);
       } else {
         scan_finish(sl[k], ring_lds + VEC * tid + k, RS, W, N, a0 + k, NR, next_pm,
                     SH ? nullptr : carry_out);
@@ -1614,10 +1391,7 @@ __device__ __forceinline__ double fold_body(const double* __restrict__ sm, int G
 #pragma unroll
       for (int u = 0; u < SUM_U; ++u) {
         if (jb + u >= T) break;
-        const double x = xs[u];
-        const double nx = isnan_d(x) ? pff : x;
-        const double ret = nx / pff - 1.0;
-        pff = nx;
+        const double ret = price_step(xs[u], pff);
         const int pos = c - (nv - W);
         if (pos >= 0) store(pos, 1.0 + ret);
         ++c;
@@ -1757,39 +1531,10 @@ __device__ __forceinline__ double scan_step_reg(ScanLane& s, double x, int m, do
                                                 int J, int64_t N, int64_t a,
                                                 double* __restrict__ R, double* __restrict__ M,
                                                 double* __restrict__ NR) {
-  const double NaN = qnan();
-  const int64_t o = (int64_t)m * N + a;
-  if (is_absent(x)) {
-    if (R) R[o] = NaN;
-    M[o] = NaN;
-    NR[o] = NaN;
-    return NaN;
-  }
-  const bool xv = !isnan_d(x);
-  const double pnew = xv ? x : s.pff;
-  const double ret = pnew / s.pff - 1.0;
-  s.pff = pnew;
-#pragma unroll
-  for (int k = 0; k + 1 < WR; ++k) fr[k] = fr[k + 1];
-  fr[WR - 1] = 1.0 + ret;
-  double acc = fr[0];
-#pragma unroll
-  for (int k = 1; k < WR; ++k)
-    if (k < (JC > 0 ? JC : J)) acc = acc * fr[k];
-  const double mom = acc - 1.0;
-  const bool ranked = !isnan_d(mom);
-  const double ps_new = xv ? x : s.psff;
-  if (s.prev >= 0) NR[(int64_t)s.prev * N + a] = ps_new / s.psff - 1.0;
-  if (ranked) {
-    s.psff = ps_new;
-    s.prev = m;
-  } else {
-    NR[o] = NaN;
-    s.prev = -1;
-  }
-  if (R) R[o] = ret;
-  M[o] = mom;
-  return mom;
+  return scan_step_on(s, x, m, N, a, R, M, NR, [&](double fct) {
+    reg_push(fr, fct);
+    return reg_prod(fr, JC > 0 ? JC : J) - 1.0;
+  });
 }
 
 // k_fold_carry's general walk for chunk g of one asset (column pointer cp, chunk stride hs):
@@ -1853,10 +1598,7 @@ __device__ __forceinline__ void tc_fold_general(const double* cp, int64_t hs, in
 #pragma unroll
       for (int u = 0; u < SUM_U; ++u) {
         if (jb + u >= T) break;
-        const double xv = xs[u];
-        const double nx = isnan_d(xv) ? pff : xv;
-        const double ret = nx / pff - 1.0;
-        pff = nx;
+        const double ret = price_step(xs[u], pff);
         const int pos = cc - (nv - W);
         if (pos >= 0) ring[pos * RS] = 1.0 + ret;
         ++cc;
@@ -1975,18 +1717,11 @@ __device__ __forceinline__ bool tc_fold_fast(const double* cp, int64_t hs, int g
 #pragma unroll
   for (int j = 0; j < T; ++j) {
     if (j >= T - nv) {
-      const double xv = win[j * RS];
-      const double nx = isnan_d(xv) ? pff : xv;
-      const double ret = nx / pff - 1.0;
-      pff = nx;
+      const double ret = price_step(win[j * RS], pff);
       if (j >= 1) fr[j - 1] = 1.0 + ret;
     }
   }
-  double acc = fr[0];
-#pragma unroll
-  for (int k = 1; k < WR; ++k)
-    if (k < J) acc = acc * fr[k];
-  const bool ranked = !isnan_d(acc - 1.0);
+  const bool ranked = !isnan_d(reg_prod(fr, J) - 1.0);
   sl.pff = last;
   sl.psff = ranked ? last : NaN;
   sl.prev = ranked ? lpm : -1;
@@ -2463,15 +2198,7 @@ __device__ __forceinline__ void shard_repair_body(
   // the pending ranked row at the shard's end: F's (= T's once converged) or T's own
   const int prev = conv ? (int)st[N + a] : t.prev;
   const double psff = conv ? st[2 * N + a] : t.psff;
-  if (prev >= 0) {
-    double nr = qnan();
-    const double x = next_pm[cj];
-    if (!is_absent(x)) {
-      const double ps_new = isnan_d(x) ? psff : x;
-      nr = ps_new / psff - 1.0;
-    }
-    NR[(int64_t)prev * N + a] = nr;
-  }
+  if (prev >= 0) NR[(int64_t)prev * N + a] = pending_finish(next_pm[cj], psff);
 }
 
 __global__ __launch_bounds__(REPAIR_THREADS) void k_shard_repair(
@@ -2578,14 +2305,8 @@ __global__ __launch_bounds__(COLS_THREADS) void k_shard_fix_cols(
           if (IDS) IDS[(int64_t)m * N + a] = (uint16_t)csm_fid(mom);
         }
       }
-      if (t.prev >= 0) {   // the pending ranked row at the shard's end (scan_finish)
-        double nr = qnan();
-        if (!is_absent(npm)) {
-          const double ps_new = isnan_d(npm) ? t.psff : npm;
-          nr = ps_new / t.psff - 1.0;
-        }
-        NR[(int64_t)t.prev * N + a] = nr;
-      }
+      // the pending ranked row at the shard's end (scan_finish)
+      if (t.prev >= 0) NR[(int64_t)t.prev * N + a] = pending_finish(npm, t.psff);
     }
     __syncthreads();   // (the LDS is the next column's)
   }

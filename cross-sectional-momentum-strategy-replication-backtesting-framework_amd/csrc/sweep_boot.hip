@@ -26,6 +26,7 @@
 // selecting inside the ranges.  The second scan repeats the whole scan's arithmetic with a range
 // test per cell: C5 rank stage 118 ms/step against 55 for bootstrap + scan + decile pass.
 #include "csm_common.h"
+#include "scan.h"
 
 #define BS_MAXJ 4
 #define BS_RW 16        // generic register ring: max(J) + skip <= 16
@@ -42,32 +43,6 @@ struct BSSet {
   uint16_t* IDS[BS_MAXJ];   // nullable together
   double* M[BS_MAXJ];
 };
-
-// Window product of look-back J (slots [RW - J - skip, RW - skip) of the shift register, oldest
-// first).  FIX: the default grid J = 3, 6, 9, 12, skip 1 with compile-time windows (J - 1
-// multiplies each); otherwise every slot predicated (acc starts at 1.0, and 1.0 * x == x, so the
-// product is the same oldest-first sequence).
-template <int RW, bool FIX>
-__device__ __forceinline__ double win_prod(const double (&f)[RW], int q, int lo, int hi) {
-  if (FIX) {
-    constexpr int Jq[4] = {3, 6, 9, 12};
-    double acc = 0.0;
-#pragma unroll
-    for (int qq = 0; qq < 4; ++qq) {
-      if (qq != q) continue;
-      const int l = RW - Jq[qq] - 1;
-      double a = f[l];
-#pragma unroll
-      for (int k = l + 1; k < RW - 1; ++k) a = a * f[k];
-      acc = a;
-    }
-    return acc;
-  }
-  double acc = 1.0;
-#pragma unroll
-  for (int k = 0; k < RW; ++k) acc = (k >= lo && k < hi) ? acc * f[k] : acc;
-  return acc;
-}
 
 // One lane per two adjacent assets of one panel (N even): column c0 = b * N + a0 of the
 // [T_m][B * N] layout.  R rows are gathered by the panel's source months, BS_CHUNK months in
@@ -128,6 +103,7 @@ __global__ __launch_bounds__(BS_THREADS, BS_MINB) void k_boot_scan(
         // k_momentum_multi_reg2's step on a present x (never NaN here).  pff and px (the shared
         // next_ret's previous price) are both the last present price, so ret doubles as the
         // pending row's next_ret below: one f64 division per asset-month instead of two
+        // (price_step restated without its forward-fill select: x is a finite product here)
         const double ret = x / pff[c] - 1.0;
         rt[c] = ret;
         // the shared next_ret also needs every factor fl(1 + ret) after the first present price
@@ -138,9 +114,7 @@ __global__ __launch_bounds__(BS_THREADS, BS_MINB) void k_boot_scan(
           if (!ab[c] && pff[c] == pff[c] && !(fabs(fr) < INFINITY && fr != 0.0)) badp = true;
         }
         pff[c] = ab[c] ? pff[c] : x;
-#pragma unroll
-        for (int k = 0; k + 1 < RW; ++k) f[c][k] = ab[c] ? f[c][k] : f[c][k + 1];
-        f[c][RW - 1] = ab[c] ? f[c][RW - 1] : 1.0 + ret;
+        reg_push(f[c], 1.0 + ret, !ab[c]);
       }
       const int64_t o = (int64_t)m * BN + c0;
       {   // shared next_ret: absent rows NaN now, present rows when the next present one comes
@@ -152,26 +126,15 @@ __global__ __launch_bounds__(BS_THREADS, BS_MINB) void k_boot_scan(
           vp[c] = rt[c];   // == x / (last present price) - 1.0
           if (!ab[c]) pc[c] = m;
         }
-        if (wp[0] >= 0 && wp[0] == wp[1]) {
-          *reinterpret_cast<double2*>(NR + (int64_t)wp[0] * BN + c0) = make_double2(vp[0], vp[1]);
-        } else {
-          if (wp[0] >= 0) NR[(int64_t)wp[0] * BN + c0] = vp[0];
-          if (wp[1] >= 0) NR[(int64_t)wp[1] * BN + c0 + 1] = vp[1];
-        }
-        if (ab[0] && ab[1]) {
-          *reinterpret_cast<double2*>(NR + o) = make_double2(NaN, NaN);
-        } else {
-          if (ab[0]) NR[o] = NaN;
-          if (ab[1]) NR[o + 1] = NaN;
-        }
+        store_next_ret_pair(NR, BN, c0, o, wp, vp, ab);
       }
 #pragma unroll
       for (int q = 0; q < BS_MAXJ; ++q) {
         if (q >= nJ) break;
         double mom[2];
 #pragma unroll
-        for (int c = 0; c < 2; ++c) mom[c] = ab[c] ? NaN : win_prod<RW, FIX>(f[c], q, lo[q], hi) - 1.0;
-        *reinterpret_cast<double2*>(js.M[q] + o) = make_double2(mom[0], mom[1]);
+        for (int c = 0; c < 2; ++c) mom[c] = ab[c] ? NaN : mj_window<RW, FIX>(f[c], q, lo[q], hi) - 1.0;
+        store_pair(js.M[q] + o, mom[0], mom[1]);
         if (with_ids)
           *reinterpret_cast<uint32_t*>(js.IDS[q] + o) = csm_fid(mom[0]) | (csm_fid(mom[1]) << 16);
       }
