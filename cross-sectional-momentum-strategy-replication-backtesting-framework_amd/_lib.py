@@ -92,6 +92,9 @@ SIGNATURES = {
     "csm_daily_returns": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _i32, _p, _p, _p, _i32,
                                          _i32, _p, _p, _p, _p]),
     "csm_series_stats": (ctypes.c_int, [_p, _p, _i32, _i32, _i64, _f64, _p]),
+    "csm_month_stats": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p]),
+    "csm_window_signals": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32,
+                                          _i32, _p, _p, _p, _p, _p, _p, _p]),
     "csm_bootstrap": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64,
                                      _f64, _p, _p]),
     "csm_boot_scan": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64, _f64,

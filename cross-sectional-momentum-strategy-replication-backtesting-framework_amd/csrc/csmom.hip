@@ -2538,9 +2538,11 @@ int csm_abi_version(void) { return CSM_ABI_VERSION; }
 
 int csm_tune_portfolio(const char* key, int value);  // portfolio.hip
 int csm_tune_ptr_portfolio(const char* key, void* p);  // portfolio.hip
+int csm_tune_signals(const char* key, int value);  // signals.hip
 
 int csm_tune(const char* key, int value) {
   if (tune_set(g_knobs, key, value) == CSM_OK) return CSM_OK;
+  if (csm_tune_signals(key, value) == CSM_OK) return CSM_OK;
   return csm_tune_portfolio(key, value);
 }
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -89,6 +90,27 @@ class DailyOut:
     DR: torch.Tensor                  # [T_d][n_bins] daily returns of the bins (NaN = no portfolio)
     DLS: torch.Tensor                 # [T_d] top minus bottom (NaN if either leg is)
     DCNT: torch.Tensor | None = None  # [T_m][K][n_bins] int32 member counts
+
+
+class MonthStats(NamedTuple):
+    """csm_month_stats (rule D1), each [T_m][N]; unpacks into window_signals' first arguments."""
+    PM: torch.Tensor    # month-end price, csm_month_end's value (ABSENT = the month has no row)
+    P1: torch.Tensor    # first priced row's price
+    HI: torch.Tensor    # maximum over the priced rows
+    SSW: torch.Tensor   # sum of squared daily returns inside the month
+    NDW: torch.Tensor   # int32, their number
+
+
+@dataclass
+class SignalsOut:
+    """csm_window_signals (rules D2..D6), each [T_m][N]; None = not asked for."""
+    SS: torch.Tensor | None = None       # SSW plus the month's first return, squared
+    ND: torch.Tensor | None = None       # int32, NDW plus one where that return exists
+    H52: torch.Tensor | None = None      # month-end price over the Jh-month high
+    RV: torch.Tensor | None = None       # realised daily volatility over Jv months (the SIG input)
+    MS: torch.Tensor | None = None       # M / RV
+    NR_H52: torch.Tensor | None = None   # next return of the H52 ranking
+    NR_MS: torch.Tensor | None = None    # next return of the MS ranking
 
 
 @dataclass
@@ -757,6 +779,56 @@ class Engine:
         self._call("csm_series_stats", _ptr(X), nS, T, nS, float(freq), _ptr(out))
         return out
 
+    def month_stats(self, P, month_start, max_month_days=None, out=None) -> MonthStats:
+        """csm_month_stats (rule D1): one pass over P for each month's last, first and highest
+        price and its sum of squared daily returns.  out = (PM, P1, HI, SSW, NDW)."""
+        T_d, N = P.shape
+        T_m = month_start.numel() - 1
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        if out is None:
+            PM, P1, HI, SSW = (self.empty((T_m, N)) for _ in range(4))
+            NDW = self.empty((T_m, N), torch.int32)
+        else:
+            PM, P1, HI, SSW, NDW = out
+            for t, name in ((PM, "PM"), (P1, "P1"), (HI, "HI"), (SSW, "SSW")):
+                _need(t, name, torch.float64, (T_m, N), self.device)
+            _need(NDW, "NDW", torch.int32, (T_m, N), self.device)
+        self._call("csm_month_stats", _ptr(P), T_d, N, _ptr(month_start), T_m,
+                   int(max_month_days), _ptr(PM), _ptr(P1), _ptr(HI), _ptr(SSW), _ptr(NDW))
+        return MonthStats(PM, P1, HI, SSW, NDW)
+
+    SIGNAL_OUTPUTS = ("SS", "ND", "H52", "RV", "MS", "NR_H52", "NR_MS")
+
+    def window_signals(self, PM, P1, HI, SSW, NDW, M=None, Jh=12, Jv=12, min_obs=None,
+                       outputs=None) -> SignalsOut:
+        """csm_window_signals (rules D2..D6) on month_stats' outputs: the 52-week high H52 over
+        Jh months, the realised daily volatility RV over Jv months (portfolio's SIG), MS = M / RV
+        for a momentum M, and the next returns of the H52 and MS rankings.  min_obs (daily
+        returns a window needs) defaults to 10 * Jv.  outputs: the SignalsOut fields to compute
+        (default: all; MS and NR_MS only with M)."""
+        T_m, N = PM.shape
+        for t, name in ((PM, "PM"), (P1, "P1"), (HI, "HI"), (SSW, "SSW")):
+            _need(t, name, torch.float64, (T_m, N), self.device)
+        _need(NDW, "NDW", torch.int32, (T_m, N), self.device)
+        if M is not None:
+            _need(M, "M", torch.float64, (T_m, N), self.device)
+        if outputs is None:
+            outputs = tuple(k for k in self.SIGNAL_OUTPUTS
+                            if M is not None or k not in ("MS", "NR_MS"))
+        unknown = set(outputs) - set(self.SIGNAL_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        min_obs = 10 * int(Jv) if min_obs is None else int(min_obs)
+        o = {k: self.empty((T_m, N), torch.int32 if k == "ND" else torch.float64)
+             for k in outputs}
+        self._call("csm_window_signals", _ptr(PM), _ptr(P1), _ptr(HI), _ptr(SSW), _ptr(NDW),
+                   _ptr(M), T_m, N, int(Jh), int(Jv), min_obs,
+                   *(_ptr(o.get(k)) for k in self.SIGNAL_OUTPUTS))
+        return SignalsOut(**o)
+
     def turnover_features(self, PM, VOL, so, mcap, lookback=3):
         """csm_turnover_features (src/features.py:60-107, rule T1): (ADV, SH, TURN, TAVG)."""
         T_m, N = PM.shape
@@ -1073,3 +1145,25 @@ class Engine:
         L, EW, CNT, NV = self.deciles(M, NR, n_bins, with_nv=True)
         LS = self.long_short(EW, CNT)
         return PipelineOut(PM=PM, M=M, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, R=R, VOL=VOL, NV=NV)
+
+    def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
+                   min_obs=None) -> PipelineOut:
+        """One full pass ranked on a signal of the daily panel: "high52", the month-end price
+        over the highest daily price of the last `window` months (no momentum scan), or
+        "mom_vol", mom_J over the realised daily volatility of the last `window` months.
+        M is the signal and NR its next return (rules D1..D6)."""
+        if signal not in ("high52", "mom_vol"):
+            raise ValueError(f"signal must be 'high52' or 'mom_vol', got {signal!r}")
+        st = self.month_stats(P, month_start)
+        if signal == "high52":
+            sig = self.window_signals(*st, Jh=window, Jv=window, min_obs=min_obs,
+                                      outputs=("H52", "NR_H52"))
+            S, NR = sig.H52, sig.NR_H52
+        else:
+            _, M, _ = self.momentum(st.PM, J, skip)
+            sig = self.window_signals(*st, M=M, Jh=window, Jv=window, min_obs=min_obs,
+                                      outputs=("MS", "NR_MS"))
+            S, NR = sig.MS, sig.NR_MS
+        L, EW, CNT, NV = self.deciles(S, NR, n_bins, with_nv=True)
+        LS = self.long_short(EW, CNT)
+        return PipelineOut(PM=st.PM, M=S, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, NV=NV)

@@ -80,7 +80,8 @@ int csm_abi_version(void);
  * 2 the prefetching one when the launch has no more (chunk, date) pairs than CUs; the same
  * bits either way), "tc_spins" (polling trips a
  * csm_signal_chunked workgroup makes before it gives up a wait, default 2^21; 0 gives up at
- * once, which only the tests of the CSM_E_TIMEOUT report set).
+ * once, which only the tests of the CSM_E_TIMEOUT report set), "stats_chunks" (csm_month_stats's
+ * month chunks: 0 auto, one month each | n >= 1 that many, clamped to T_m).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -602,6 +603,57 @@ int csm_daily_returns(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
  */
 int csm_series_stats(csm_ctx* ctx, const double* X, int32_t nS, int32_t T, int64_t stride,
                      double freq, double* out);
+
+/*
+ * Signals that need every day row of the panel (rules D1..D6 in DESIGN.md section 7; no
+ * reference counterpart): the 52-week high and volatility-scaled momentum.  A row d of column a
+ * is priced when P[d][a] is not NaN (the ABSENT payload counts as NaN); month t covers the rows
+ * [month_start[t], month_start[t+1]).  fp64 throughout, every sum sequential in the stated order
+ * from 0.0, so two calls, and every launch shape, give the same bits.
+ *
+ * csm_month_stats (D1): one pass over P; per (month, asset), independent of every other month:
+ *   PM  [T_m][N] nullable out: csm_month_end's value -- the last priced row's price, NaN when the
+ *       month has a row but no price, ABSENT when it has no row (or no day at all)
+ *   P1  [T_m][N] out: the first priced row's price, NaN if none
+ *   HI  [T_m][N] out: the maximum over the priced rows, NaN if none
+ *   SSW [T_m][N] out, NDW [T_m][N] int32 out: over each pair of consecutive priced rows d' < d of
+ *       the month, in day order, r = P[d] / P[d'] - 1, SSW += r * r, NDW += 1 (rows without a
+ *       price in between are crossed: one return, booked where the price reappears)
+ *   max_month_days: an upper bound of the months' lengths in rows, in [1, 32] (the bound
+ *       csm_signal and csm_daily_returns take; a longer month is the caller's breach)
+ * Any N >= 1; even N with 16-B aligned P / PM / P1 / HI / SSW and 8-B aligned NDW takes two
+ * assets per lane, the same bits.  The launch is (asset slices) x (chunks of consecutive months);
+ * "stats_chunks" (csm_tune: 0 auto, one month per chunk | n >= 1 that many chunks, clamped to T_m)
+ * only changes how many workgroups there are.  Rows outside
+ * [month_start[0], month_start[T_m]) are never read.
+ *
+ * csm_window_signals (D2..D6): a scan over the months of csm_month_stats's outputs, per asset:
+ *   q = the last priced PM of the months before t.  When P1[t] is priced and q is not NaN:
+ *       r0 = P1[t] / q - 1, SS[t] = SSW[t] + r0 * r0, ND[t] = NDW[t] + 1 (the month's first
+ *       return, added last); else SS = SSW, ND = NDW.  first = the asset's first priced month.
+ *   H52[t] = PM[t] / max{HI[j] : t-Jh+1 <= j <= t, HI[j] not NaN}: defined iff PM[t] is priced,
+ *       t-Jh+1 >= 0 and first <= t-Jh+1; always <= 1
+ *   RV[t] = sqrt(S / n), S = sum SS[j], n = sum ND[j] over j = t-Jv+1 .. t, oldest first: defined
+ *       iff t-Jv+1 >= 0, first <= t-Jv+1 and n >= min_obs (month t itself may have no row); the
+ *       realised daily volatility, and the SIG input of csm_portfolio's cost model
+ *   MS[t] = M[t] / RV[t]: defined iff both are not NaN and RV[t] > 0
+ *   NR_H52 / NR_MS: the next return of the signal S = H52 / MS under csm_momentum's rule --
+ *       ranked = (PM not ABSENT) and (S not NaN), return over the prices forward-filled within
+ *       the ranked subset, settled by the asset's next present row; whole panels only (the last
+ *       ranked row's is NaN)
+ *   M nullable [T_m][N]: the momentum to scale (csm_momentum's M of any J, skip)
+ *   1 <= Jh, Jv <= 36;  min_obs >= 1;  T_m >= 1;  any N >= 1
+ *   SS, H52, RV, MS, NR_H52, NR_MS [T_m][N] out, ND [T_m][N] int32 out: NaN where not defined;
+ *       every one nullable; MS and NR_MS need M
+ * +-inf and zero or negative prices are out of contract.
+ */
+int csm_month_stats(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
+                    const int64_t* month_start, int32_t T_m, int32_t max_month_days, double* PM,
+                    double* P1, double* HI, double* SSW, int32_t* NDW);
+int csm_window_signals(csm_ctx* ctx, const double* PM, const double* P1, const double* HI,
+                       const double* SSW, const int32_t* NDW, const double* M, int32_t T_m,
+                       int64_t N, int32_t Jh, int32_t Jv, int32_t min_obs, double* SS, int32_t* ND,
+                       double* H52, double* RV, double* MS, double* NR_H52, double* NR_MS);
 
 /*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
