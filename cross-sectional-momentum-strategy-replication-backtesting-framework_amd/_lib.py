@@ -95,6 +95,10 @@ SIGNATURES = {
     "csm_month_stats": (ctypes.c_int, [_p, _p, _i64, _i64, _p, _i32, _i32, _p, _p, _p, _p, _p]),
     "csm_window_signals": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32,
                                           _i32, _p, _p, _p, _p, _p, _p, _p]),
+    "csm_market_factor": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _p, _p, _p]),
+    "csm_market_model": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, _i32, _i32, _i32, _p, _p,
+                                        _p, _p, _p]),
+    "csm_next_ret": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p]),
     "csm_bootstrap": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64,
                                      _f64, _p, _p]),
     "csm_boot_scan": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64, _f64,

@@ -46,6 +46,8 @@ struct csm_ctx {
   void* planes_ws[32];
   unsigned char planes_bits[32];
   int planes_next;
+  void* mkt_ws;           // csm_market_factor's per-slice partial sums and counts (market.hip),
+  size_t mkt_ws_bytes;    // grown lazily
 };
 
 static inline int set_err(csm_ctx* c, int code, const char* fmt, ...) {

@@ -2539,10 +2539,12 @@ int csm_abi_version(void) { return CSM_ABI_VERSION; }
 int csm_tune_portfolio(const char* key, int value);  // portfolio.hip
 int csm_tune_ptr_portfolio(const char* key, void* p);  // portfolio.hip
 int csm_tune_signals(const char* key, int value);  // signals.hip
+int csm_tune_market(const char* key, int value);  // market.hip
 
 int csm_tune(const char* key, int value) {
   if (tune_set(g_knobs, key, value) == CSM_OK) return CSM_OK;
   if (csm_tune_signals(key, value) == CSM_OK) return CSM_OK;
+  if (csm_tune_market(key, value) == CSM_OK) return CSM_OK;
   return csm_tune_portfolio(key, value);
 }
 
@@ -2587,8 +2589,9 @@ int csm_create(int device, csm_ctx** out) {
 
 int csm_destroy(csm_ctx* ctx) {
   if (ctx) (void)csm_allgather_free(ctx);
-  if (ctx && (ctx->scratch || ctx->dec_flg || ctx->ticket || ctx->dsplit)) {
+  if (ctx && (ctx->scratch || ctx->dec_flg || ctx->ticket || ctx->dsplit || ctx->mkt_ws)) {
     (void)hipSetDevice(ctx->device);
+    if (ctx->mkt_ws) (void)hipFree(ctx->mkt_ws);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->dec_flg) (void)hipFree(ctx->dec_flg);
     if (ctx->ticket) (void)hipFree(ctx->ticket);

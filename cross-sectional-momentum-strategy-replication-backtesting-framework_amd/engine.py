@@ -114,6 +114,17 @@ class SignalsOut:
 
 
 @dataclass
+class MarketModelOut:
+    """csm_market_model (rules B3..B5), each [T_m][N]; None = not asked for."""
+    BETA: torch.Tensor | None = None     # slope of the asset's month returns on the factor
+    ALPHA: torch.Tensor | None = None    # intercept
+    IVOL: torch.Tensor | None = None     # residual standard deviation, n - 2 degrees of freedom
+    RESMOM: torch.Tensor | None = None   # residual momentum: sum of residuals over their deviation
+    NOBS: torch.Tensor | None = None     # int32, observations in the window
+    F: torch.Tensor | None = None        # [T_m] the factor regressed on (MKT when none was given)
+
+
+@dataclass
 class ShardState:
     """signal_shard's end-state record [5][N] (present months, pending ranked row, its
     subset-ffilled price, first / last present month) with the daily panel it came from
@@ -829,6 +840,56 @@ class Engine:
                    *(_ptr(o.get(k)) for k in self.SIGNAL_OUTPUTS))
         return SignalsOut(**o)
 
+    def market_factor(self, PM, min_assets=1, with_x=False):
+        """csm_market_factor (rules B1, B2): the equal-weight market return MKT [T_m] of the
+        month returns x over calendar-adjacent priced months, and NMK [T_m] (int32) the assets
+        behind each.  Returns (MKT, NMK), or (MKT, NMK, X) with_x."""
+        T_m, N = PM.shape
+        _need(PM, "PM", torch.float64, (T_m, N), self.device)
+        MKT = self.empty((T_m,))
+        NMK = self.empty((T_m,), torch.int32)
+        X = self.empty((T_m, N)) if with_x else None
+        self._call("csm_market_factor", _ptr(PM), T_m, N, int(min_assets), _ptr(X), _ptr(MKT),
+                   _ptr(NMK))
+        return (MKT, NMK, X) if with_x else (MKT, NMK)
+
+    MARKET_OUTPUTS = ("BETA", "ALPHA", "IVOL", "RESMOM", "NOBS")
+
+    def market_model(self, PM, F=None, window=36, J=12, skip=1, min_obs=None,
+                     outputs=None) -> MarketModelOut:
+        """csm_market_model (rules B3..B5): each asset's month returns regressed on the factor F
+        [T_m] over `window` calendar months -- BETA, ALPHA, the idiosyncratic volatility IVOL, the
+        residual momentum RESMOM over the J months that end `skip` months back, and NOBS.  F None:
+        market_factor's MKT.  min_obs defaults to max(2, ceil(2 * window / 3)).  outputs: the
+        MarketModelOut fields to compute (default: all)."""
+        T_m, N = PM.shape
+        _need(PM, "PM", torch.float64, (T_m, N), self.device)
+        if F is None:
+            F, _ = self.market_factor(PM)
+        _need(F, "F", torch.float64, (T_m,), self.device)
+        outputs = self.MARKET_OUTPUTS if outputs is None else tuple(outputs)
+        unknown = set(outputs) - set(self.MARKET_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = max(2, -(-2 * window // 3)) if min_obs is None else int(min_obs)
+        o = {k: self.empty((T_m, N), torch.int32 if k == "NOBS" else torch.float64)
+             for k in outputs}
+        self._call("csm_market_model", _ptr(PM), _ptr(F), T_m, N, window, int(J), int(skip),
+                   min_obs, *(_ptr(o.get(k)) for k in self.MARKET_OUTPUTS))
+        return MarketModelOut(F=F, **o)
+
+    def next_ret(self, PM, S, out=None):
+        """csm_next_ret (rule B6): the next return NR [T_m][N] of any signal S [T_m][N], which
+        deciles and portfolio then rank on."""
+        T_m, N = PM.shape
+        _need(PM, "PM", torch.float64, (T_m, N), self.device)
+        _need(S, "S", torch.float64, (T_m, N), self.device)
+        NR = self.empty((T_m, N)) if out is None else out
+        _need(NR, "NR", torch.float64, (T_m, N), self.device)
+        self._call("csm_next_ret", _ptr(PM), _ptr(S), T_m, N, _ptr(NR))
+        return NR
+
     def turnover_features(self, PM, VOL, so, mcap, lookback=3):
         """csm_turnover_features (src/features.py:60-107, rule T1): (ADV, SH, TURN, TAVG)."""
         T_m, N = PM.shape
@@ -1146,16 +1207,30 @@ class Engine:
         LS = self.long_short(EW, CNT)
         return PipelineOut(PM=PM, M=M, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, R=R, VOL=VOL, NV=NV)
 
+    MARKET_SIGNALS = {"resid_mom": "RESMOM", "beta": "BETA", "ivol": "IVOL"}
+    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS)
+
     def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
                    min_obs=None) -> PipelineOut:
         """One full pass ranked on a signal of the daily panel: "high52", the month-end price
         over the highest daily price of the last `window` months (no momentum scan), or
         "mom_vol", mom_J over the realised daily volatility of the last `window` months.
-        M is the signal and NR its next return (rules D1..D6)."""
-        if signal not in ("high52", "mom_vol"):
-            raise ValueError(f"signal must be 'high52' or 'mom_vol', got {signal!r}")
+        M is the signal and NR its next return (rules D1..D6).
+        Or on a signal of the monthly cross-section (rules B1..B6), from the market model of each
+        asset's month returns on the equal-weight market over `window` months: "resid_mom", the
+        residual momentum of the J months that end `skip` months back, "beta" or "ivol".  For
+        these three a `window` left at its default of 12 means 36, and min_obs counts months
+        (default max(2, ceil(2 * window / 3)))."""
+        if signal not in self.RUN_SIGNALS:
+            raise ValueError(f"signal must be one of {self.RUN_SIGNALS}, got {signal!r}")
         st = self.month_stats(P, month_start)
-        if signal == "high52":
+        if signal in self.MARKET_SIGNALS:
+            field = self.MARKET_SIGNALS[signal]
+            mm = self.market_model(st.PM, window=36 if window == 12 else window, J=J, skip=skip,
+                                   min_obs=min_obs, outputs=(field,))
+            S = getattr(mm, field)
+            NR = self.next_ret(st.PM, S)
+        elif signal == "high52":
             sig = self.window_signals(*st, Jh=window, Jv=window, min_obs=min_obs,
                                       outputs=("H52", "NR_H52"))
             S, NR = sig.H52, sig.NR_H52

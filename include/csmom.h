@@ -81,7 +81,8 @@ int csm_abi_version(void);
  * bits either way), "tc_spins" (polling trips a
  * csm_signal_chunked workgroup makes before it gives up a wait, default 2^21; 0 gives up at
  * once, which only the tests of the CSM_E_TIMEOUT report set), "stats_chunks" (csm_month_stats's
- * month chunks: 0 auto, one month each | n >= 1 that many, clamped to T_m).
+ * month chunks: 0 auto, one month each | n >= 1 that many, clamped to T_m), "mm_chunks"
+ * (csm_market_model's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -654,6 +655,58 @@ int csm_window_signals(csm_ctx* ctx, const double* PM, const double* P1, const d
                        const double* SSW, const int32_t* NDW, const double* M, int32_t T_m,
                        int64_t N, int32_t Jh, int32_t Jv, int32_t min_obs, double* SS, int32_t* ND,
                        double* H52, double* RV, double* MS, double* NR_H52, double* NR_MS);
+
+/*
+ * Signals of the monthly cross-section (rules B1..B6 in DESIGN.md section 7; no reference
+ * counterpart): the equal-weight market return, each asset's market model on it -- beta, alpha,
+ * idiosyncratic volatility and residual momentum (Blitz, Huij and Martens 2011) -- and the next
+ * return of any signal.  A month price is priced when it is not NaN (the ABSENT payload counts as
+ * NaN).  fp64 throughout; every per-asset sum is sequential in the stated order from 0.0, so two
+ * calls, and every launch shape, give the same bits.
+ *
+ * csm_market_factor (B1, B2), PM [T_m][N] (csm_month_end's or csm_month_stats's):
+ *   X   [T_m][N] nullable out: x[t] = PM[t] / PM[t-1] - 1 when both calendar-adjacent month
+ *       prices are priced, else NaN (x[0] is NaN).  Not csm_momentum's R, which forward-fills over
+ *       gaps; on a panel with every cell priced the two are equal bit for bit.
+ *   NMK [T_m] int32 nullable out: the assets with an observation in month t
+ *   MKT [T_m] out: (sum of x[t] over those assets) / NMK[t] when NMK[t] >= min_assets (>= 1), else
+ *       NaN.  The sum's order is a function of N alone (lanes a fixed stride apart, a halving
+ *       tree, then slices of 2048 assets in index order): no atomic, and no csm_tune knob
+ *       changes it.  |MKT - exact| <= 2^-53 * (sum |x| + |MKT|).
+ *
+ * csm_market_model (B3..B5) over the Wb calendar months j = t-Wb+1 .. t (t-Wb+1 >= 0), x as above
+ * (computed from PM), f = F[j] (F [T_m] on the device: MKT, or any series of the caller's):
+ *   observations: the window's months where x[j] and f[j] are both not NaN; n their number
+ *   pass 1, oldest first: sx += x, sf += f; mx = sx / n, mf = sf / n
+ *   pass 2, oldest first: df = f - mf, dx = x - mx, sff += df * df, sfx += df * dx
+ *   BETA[t] = sfx / sff, ALPHA[t] = mx - BETA * mf: defined iff n >= min_obs and sff > 0
+ *   NOBS[t] = n (int32; 0 before the first whole window)
+ *   e[j] = x[j] - (ALPHA + BETA * f[j]) on the observations, with month t's coefficients
+ *   IVOL[t] = sqrt((sum e[j]^2, oldest first) / (n - 2)): defined iff BETA is and n >= 3
+ *   RESMOM[t]: over the formation months j = t-skip-J+1 .. t-skip, se = sum e[j] oldest first,
+ *       me = se / J, sv = sum (e[j] - me)^2 oldest first, RESMOM = se / sqrt(sv / (J - 1)):
+ *       defined iff BETA is, all J formation months are observations, and sv > 0
+ *   2 <= Wb <= 60;  min_obs in [2, Wb];  J >= 2, skip >= 0 and J + skip <= Wb, checked only when
+ *   RESMOM is requested;  T_m >= 1 (T_m < Wb: nothing is defined);  any N >= 1
+ *   BETA, ALPHA, IVOL, RESMOM [T_m][N] out, NOBS [T_m][N] int32 out: NaN where not defined; every
+ *       one nullable, at least one given
+ * The launch is (64 assets) x (chunks of consecutive months), each chunk starting cold Wb - 1
+ * months before its first; "mm_chunks" (csm_tune: 0 auto | n >= 1 that many, clamped to T_m) only
+ * changes how many workgroups there are.
+ *
+ * csm_next_ret (B6): NR [T_m][N] out, the next return of the signal S [T_m][N] under
+ * csm_momentum's rule -- ranked = (PM not ABSENT) and (S not NaN), return over the prices
+ * forward-filled within the ranked subset, settled by the asset's next present row; whole panels
+ * only (the last ranked row's is NaN).  With it csm_deciles and csm_portfolio rank any signal.
+ * +-inf and zero or negative prices are out of contract.
+ */
+int csm_market_factor(csm_ctx* ctx, const double* PM, int32_t T_m, int64_t N, int32_t min_assets,
+                      double* X, double* MKT, int32_t* NMK);
+int csm_market_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_m, int64_t N,
+                     int32_t Wb, int32_t J, int32_t skip, int32_t min_obs, double* BETA,
+                     double* ALPHA, double* IVOL, double* RESMOM, int32_t* NOBS);
+int csm_next_ret(csm_ctx* ctx, const double* PM, const double* S, int32_t T_m, int64_t N,
+                 double* NR);
 
 /*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
