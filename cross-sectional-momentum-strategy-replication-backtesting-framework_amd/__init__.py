@@ -19,16 +19,20 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.run_signal                     momentum from every day row (rules D1..D6; beyond the reference)
   Engine.market_factor / market_model   equal-weight market, beta, idiosyncratic volatility and
   Engine.next_ret                       residual momentum; the next return of any signal (B1..B6)
+  Engine.xs_regress / newey_west        per-month cross-sectional regressions (OLS, WLS, ridge) and
+  Engine.fama_macbeth / fama_macbeth    Newey-West t-statistics of any monthly series (R1..R6)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyOut, Engine, MarketModelOut, MonthStats, PipelineOut, PortfolioOut,
-                     SignalsOut, absent_tensor, is_absent, quantile_table)
+from .engine import (DailyOut, Engine, FamaMacBethOut, MarketModelOut, MonthStats, NeweyWestOut,
+                     PipelineOut, PortfolioOut, SignalsOut, XsRegressOut, absent_tensor, is_absent,
+                     quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
 from .features import compute_monthly_momentum_from_daily, compute_monthly_turnover, get_engine
 from .lesw import DoubleSortResult, momentum_volume_double_sort
+from .regress import FamaMacBethResult, fama_macbeth
 from .panel import DensePanel, from_long, month_offsets, monthly_frame
 from .replication import (ReplicationResult, assign_deciles_per_date, daily_portfolio_returns,
                           monthly_replication)
@@ -44,5 +48,6 @@ __all__ = [
     "DensePanel", "from_long", "month_offsets", "monthly_frame", "ReplicationResult",
     "assign_deciles_per_date", "monthly_replication", "ensure_dir", "save_plot", "sharpe",
     "DailyOut", "daily_portfolio_returns", "MonthStats", "SignalsOut",
-    "MarketModelOut",
+    "MarketModelOut", "XsRegressOut", "NeweyWestOut", "FamaMacBethOut", "FamaMacBethResult",
+    "fama_macbeth",
 ]

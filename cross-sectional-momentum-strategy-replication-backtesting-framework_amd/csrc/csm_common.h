@@ -48,6 +48,8 @@ struct csm_ctx {
   int planes_next;
   void* mkt_ws;           // csm_market_factor's per-slice partial sums and counts (market.hip),
   size_t mkt_ws_bytes;    // grown lazily
+  void* xs_ws;            // csm_xs_regress's per-slice partial sums and counts, or a series too
+  size_t xs_ws_bytes;     // long for csm_newey_west's LDS (xsreg.hip), grown lazily
 };
 
 static inline int set_err(csm_ctx* c, int code, const char* fmt, ...) {

@@ -2589,8 +2589,10 @@ int csm_create(int device, csm_ctx** out) {
 
 int csm_destroy(csm_ctx* ctx) {
   if (ctx) (void)csm_allgather_free(ctx);
-  if (ctx && (ctx->scratch || ctx->dec_flg || ctx->ticket || ctx->dsplit || ctx->mkt_ws)) {
+  if (ctx && (ctx->scratch || ctx->dec_flg || ctx->ticket || ctx->dsplit || ctx->mkt_ws ||
+              ctx->xs_ws)) {
     (void)hipSetDevice(ctx->device);
+    if (ctx->xs_ws) (void)hipFree(ctx->xs_ws);
     if (ctx->mkt_ws) (void)hipFree(ctx->mkt_ws);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->dec_flg) (void)hipFree(ctx->dec_flg);

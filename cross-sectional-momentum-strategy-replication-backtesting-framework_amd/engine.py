@@ -125,6 +125,34 @@ class MarketModelOut:
 
 
 @dataclass
+class XsRegressOut:
+    """csm_xs_regress (rules R1..R5): one cross-sectional regression per month."""
+    GAMMA: torch.Tensor                  # [T_m][K + 1] intercept, then one slope per signal
+    R2: torch.Tensor                     # [T_m]
+    NOBS: torch.Tensor                   # [T_m] int32, the month's observations
+
+
+@dataclass
+class NeweyWestOut:
+    """csm_newey_west (rule R6), each [C] (0-d for a [T] series)."""
+    MEAN: torch.Tensor                   # time-series mean of the non-NaN entries
+    SE: torch.Tensor                     # its Newey-West standard error
+    T: torch.Tensor                      # MEAN / SE
+    NT: torch.Tensor                     # int32, the non-NaN entries
+
+
+@dataclass
+class FamaMacBethOut(XsRegressOut):
+    """Engine.fama_macbeth: the per-month regressions and the summary of their coefficients."""
+    MEAN: torch.Tensor | None = None     # [K + 1] time-series means of GAMMA's columns
+    SE: torch.Tensor | None = None       # [K + 1]
+    T: torch.Tensor | None = None        # [K + 1]
+    NT: torch.Tensor | None = None       # [K + 1] int32, months behind each
+    R2_MEAN: torch.Tensor | None = None  # 0-d, the mean of the months' R2
+    lags: int = 0                        # Newey-West lags used
+
+
+@dataclass
 class ShardState:
     """signal_shard's end-state record [5][N] (present months, pending ranked row, its
     subset-ffilled price, first / last present month) with the daily panel it came from
@@ -889,6 +917,63 @@ class Engine:
         _need(NR, "NR", torch.float64, (T_m, N), self.device)
         self._call("csm_next_ret", _ptr(PM), _ptr(S), T_m, N, _ptr(NR))
         return NR
+
+    def xs_regress(self, Y, signals, W=None, standardize=False, ridge=0.0,
+                   min_obs=None) -> XsRegressOut:
+        """csm_xs_regress (rules R1..R5): each month's regression of Y [T_m][N] on the K signals
+        (a sequence of [T_m][N] tensors, 1 <= K <= 8) across the assets -- OLS, WLS with weights
+        W, and with standardize / ridge the reference's StandardScaler + Ridge on the month's
+        cross-section.  min_obs defaults to K + 2."""
+        signals = list(signals)
+        T_m, N = Y.shape
+        _need(Y, "Y", torch.float64, (T_m, N), self.device)
+        for k, S in enumerate(signals):
+            _need(S, f"signals[{k}]", torch.float64, (T_m, N), self.device)
+        if W is not None:
+            _need(W, "W", torch.float64, (T_m, N), self.device)
+        K = len(signals)
+        min_obs = K + 2 if min_obs is None else int(min_obs)
+        GAMMA = self.empty((T_m, K + 1))
+        R2 = self.empty((T_m,))
+        NOBS = self.empty((T_m,), torch.int32)
+        ptrs = (ctypes.c_void_p * max(K, 1))(*[S.data_ptr() for S in signals])
+        self._call("csm_xs_regress", _ptr(Y), ptrs, K, _ptr(W), T_m, N, int(bool(standardize)),
+                   float(ridge), min_obs, _ptr(GAMMA), _ptr(R2), _ptr(NOBS))
+        return XsRegressOut(GAMMA=GAMMA, R2=R2, NOBS=NOBS)
+
+    @staticmethod
+    def default_lags(T):
+        """The Newey-West lag rule floor(4 (T / 100)^(2/9))."""
+        return int(np.floor(4.0 * (T / 100.0) ** (2.0 / 9.0)))
+
+    def newey_west(self, G, lags=None) -> NeweyWestOut:
+        """csm_newey_west (rule R6): the time-series mean of each column of G [T][C] (or of one
+        series [T]) over its non-NaN entries, its Newey-West standard error (Bartlett kernel) and
+        t-statistic.  lags defaults to floor(4 (T / 100)^(2/9)).  G is any per-month series:
+        xs_regress's GAMMA, PipelineOut.EW / LS, PortfolioOut.LS."""
+        one = G.dim() == 1
+        G2 = G.unsqueeze(1) if one else G
+        T, C = G2.shape
+        _need(G2, "G", torch.float64, (T, C), self.device)
+        lags = self.default_lags(T) if lags is None else int(lags)
+        MEAN, SE, TS = (self.empty((C,)) for _ in range(3))
+        NT = self.empty((C,), torch.int32)
+        self._call("csm_newey_west", _ptr(G2), T, C, C, lags, _ptr(MEAN), _ptr(SE), _ptr(TS),
+                   _ptr(NT))
+        if one:
+            MEAN, SE, TS, NT = MEAN[0], SE[0], TS[0], NT[0]
+        return NeweyWestOut(MEAN=MEAN, SE=SE, T=TS, NT=NT)
+
+    def fama_macbeth(self, Y, signals, W=None, standardize=True, ridge=0.0, min_obs=None,
+                     lags=None) -> FamaMacBethOut:
+        """Fama-MacBeth: xs_regress per month, then newey_west over GAMMA's K + 1 columns and the
+        mean of R2, chained on the device."""
+        r = self.xs_regress(Y, signals, W, standardize, ridge, min_obs)
+        lags = self.default_lags(Y.shape[0]) if lags is None else int(lags)
+        nw = self.newey_west(r.GAMMA, lags)
+        r2 = self.newey_west(r.R2, lags)
+        return FamaMacBethOut(GAMMA=r.GAMMA, R2=r.R2, NOBS=r.NOBS, MEAN=nw.MEAN, SE=nw.SE, T=nw.T,
+                              NT=nw.NT, R2_MEAN=r2.MEAN, lags=lags)
 
     def turnover_features(self, PM, VOL, so, mcap, lookback=3):
         """csm_turnover_features (src/features.py:60-107, rule T1): (ADV, SH, TURN, TAVG)."""

@@ -1,0 +1,94 @@
+"""Fama-MacBeth (1973) regressions from a daily frame: next month's return regressed each month
+on the engine's signals across the assets, the monthly slopes averaged over time and judged by
+Newey-West t-statistics (rules R1..R6 in DESIGN.md section 7; Engine.fama_macbeth).
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import numpy as np
+import pandas as pd
+import torch
+
+from .engine import Engine
+from .features import get_engine, upload_panel
+from .panel import from_long
+
+SIGNAL_NAMES = ("mom", "rev", *Engine.RUN_SIGNALS)
+
+
+@dataclass
+class FamaMacBethResult:
+    table: pd.DataFrame       # one row per coefficient ('const', then the signals): mean, se, t, months
+    gammas: pd.DataFrame      # the per-month coefficients, indexed by month-end date
+    r2: pd.Series             # the per-month R2
+    nobs: pd.Series           # the per-month observations
+    r2_mean: float
+    lags: int
+
+
+def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None):
+    """The named signals of a daily panel on the device, each [T_m][N], with the B1 month return
+    X: "mom" (mom_J), "rev" (the month's own return) and Engine.RUN_SIGNALS' names, built by the
+    calls run_signal makes.  window None: 12 months for the daily signals, 36 for the market
+    model's."""
+    unknown = [n for n in names if n not in SIGNAL_NAMES]
+    if unknown:
+        raise ValueError(f"signals must be among {SIGNAL_NAMES}, got {unknown}")
+    st = eng.month_stats(P, month_start)
+    _, _, X = eng.market_factor(st.PM, with_x=True)
+    out = {}
+    if "rev" in names:
+        out["rev"] = X
+    if "mom" in names or "mom_vol" in names:
+        _, M, _ = eng.momentum(st.PM, J, skip)
+        out["mom"] = M
+    daily = [n for n in ("high52", "mom_vol") if n in names]
+    if daily:
+        wd = 12 if window is None else int(window)
+        fields = {"high52": "H52", "mom_vol": "MS"}
+        sig = eng.window_signals(*st, M=out.get("mom"), Jh=wd, Jv=wd,
+                                 outputs=tuple(fields[n] for n in daily))
+        for n in daily:
+            out[n] = getattr(sig, fields[n])
+    market = [n for n in names if n in Engine.MARKET_SIGNALS]
+    if market:
+        mm = eng.market_model(st.PM, window=36 if window is None else int(window), J=J, skip=skip,
+                              outputs=tuple(Engine.MARKET_SIGNALS[n] for n in market))
+        for n in market:
+            out[n] = getattr(mm, Engine.MARKET_SIGNALS[n])
+    return [out[n] for n in names], X
+
+
+def fama_macbeth(daily_df, signals=("mom", "high52", "beta", "ivol"), J=12, skip=1, window=None,
+                 weights=None, standardize=True, ridge=0.0, lags=None, device=None):
+    """Fama-MacBeth regressions of next month's return on the named signals.  Y[t] is the month
+    return (rule B1) of month t + 1; weights, when given, is a [T_m][N] array or tensor in the
+    dense panel's layout (from_long).  Returns a FamaMacBethResult, or None when the frame holds
+    no month."""
+    names = tuple(signals)
+    panel = from_long(daily_df)
+    if panel.P.size == 0 or panel.T_m == 0:
+        return None
+    eng = get_engine(device)
+    P, _, ms = upload_panel(panel, eng, with_volume=False)
+    S, X = build_signals(eng, P, ms, names, J, skip, window)
+    Y = torch.cat([X[1:], torch.full_like(X[:1], float("nan"))])
+    W = None
+    if weights is not None:
+        W = torch.as_tensor(np.ascontiguousarray(weights) if isinstance(weights, np.ndarray)
+                            else weights, dtype=torch.float64).to(eng.device).contiguous()
+    out = eng.fama_macbeth(Y, S, W, standardize, ridge, lags=lags)
+    idx = pd.DatetimeIndex(panel.month_end, name="date")
+    cols = ["const", *names]
+    table = pd.DataFrame({"mean": out.MEAN.cpu().numpy(), "se": out.SE.cpu().numpy(),
+                          "t": out.T.cpu().numpy(), "months": out.NT.cpu().numpy()},
+                         index=pd.Index(cols, name="coefficient"))
+    return FamaMacBethResult(
+        table=table, gammas=pd.DataFrame(out.GAMMA.cpu().numpy(), index=idx, columns=cols),
+        r2=pd.Series(out.R2.cpu().numpy(), index=idx, name="r2"),
+        nobs=pd.Series(out.NOBS.cpu().numpy(), index=idx, name="nobs"),
+        r2_mean=float(out.R2_MEAN), lags=out.lags)
+
+
+__all__ = ["FamaMacBethResult", "SIGNAL_NAMES", "build_signals", "fama_macbeth"]

@@ -709,6 +709,53 @@ int csm_next_ret(csm_ctx* ctx, const double* PM, const double* S, int32_t T_m, i
                  double* NR);
 
 /*
+ * Fama-MacBeth (1973) cross-sectional regressions (rules R1..R6 in DESIGN.md section 7; the
+ * reference's StandardScaler + Ridge, src/models.py:8-22, is the standardize = 1, ridge > 0 case
+ * applied to one month's cross-section).  fp64 throughout, every sum in a stated order, so two
+ * calls, and every launch shape, give the same bits.
+ *
+ * csm_xs_regress: month t's regression of Y[t] on S_0[t] .. S_{K-1}[t] across the assets.
+ *   Y [T_m][N]; S a HOST array of K device pointers, each [T_m][N] (1 <= K <= 8); W [T_m][N]
+ *   nullable weights.  Asset a is an observation of month t iff Y and every S_k are not NaN (the
+ *   ABSENT payload counts as NaN) and, with W, W is not NaN and > 0.  Months are independent.
+ *   R1  every sum over the assets: non-observations add 0.0; slices of 2048 assets; lane l of 256
+ *       adds assets 2048 i + l + 256 k, k = 0..7, in k order from 0.0; each 64 consecutive lanes by
+ *       a halving tree (h = 32..1: element j < h += element j + h); the four wave sums in order
+ *       from 0.0; the slice sums in order from 0.0.  A function of N alone: no atomic, no knob.
+ *   R2  w = 1.0 without W.  n = observations = NOBS[t] (int32, nullable, written for every month);
+ *       sw = sum w, sy = sum w * y, ss_k = sum w * s_k; my = sy / sw, ms_k = ss_k / sw.
+ *       n < min_obs (min_obs >= K + 2): every float output of the month is NaN.
+ *   R3  dy = y - my, d_k = s_k - ms_k; C_jk = sum (w * d_j) * d_k (j <= k), c_k = sum (w * d_k) * dy,
+ *       cyy = sum (w * dy) * dy.  The month is undefined unless every C_kk > 0 and cyy > 0.
+ *   R4  standardize: sd_k = sqrt(C_kk / sw), A0_jk = C_jk / (sd_j * sd_k), b_k = c_k / sd_k (the
+ *       population z-score); else A0 = C, b = c.  A = A0 with A_kk = A0_kk + ridge (ridge >= 0).
+ *   R5  one lane, sequentially.  Cholesky, j = 0..K-1: d = A_jj, d = d - L_jp * L_jp (p < j
+ *       ascending); undefined unless d > A_jj * 2^-40; L_jj = sqrt(d); for i > j: v = A_ij,
+ *       v = v - L_ip * L_jp (p < j ascending), L_ij = v / L_jj.  Forward: z_j = (b_j - s) / L_jj,
+ *       s = sum_{p<j} L_jp * z_p ascending from 0.0.  Back, j = K-1..0: g_j = (z_j - s) / L_jj,
+ *       s = sum_{p>j} L_pj * g_p ascending from 0.0.  Intercept: g0 = my standardised, else
+ *       g0 = my, g0 = g0 - g_k * ms_k in k order.  Fit: gb = sum g_j * b_j, gAg = sum_j g_j *
+ *       (sum_k A0_jk * g_k), each ascending from 0.0; rss = (cyy - 2.0 * gb) + gAg;
+ *       R2 = 1.0 - rss / cyy.
+ *   GAMMA [T_m][K + 1] out = (g0, g_0 .. g_{K-1}); R2 [T_m] nullable out; NaN where undefined.
+ *   CSM_E_INVAL: K outside [1, 8], min_obs < K + 2, ridge < 0 or not finite, a NULL Y / S / S[k] /
+ *   GAMMA, T_m < 1, N < 1, T_m * N > 2^40.  +-inf in the data is out of contract.
+ * *
+ * csm_newey_west (R6): per column c of G (entry i at G[i * ld + c], ld >= C), the non-NaN entries
+ * in time order x_1 .. x_n (gaps closed): NT = n (int32); MEAN = (sum x in order from 0.0) / n
+ * (NaN when n = 0); u_i = x_i - MEAN; a_l = (sum_{i>l} u_i * u_{i-l}, i ascending) / n for
+ * l = 0..lags; var = a_0, then var += (2.0 * (1.0 - l / (lags + 1.0))) * a_l, l ascending (the
+ * Bartlett kernel, 1/n scaling, no small-sample correction); SE = sqrt(var / n), TSTAT = MEAN / SE,
+ * both defined iff n >= lags + 2 and var > 0.  MEAN [C] out; SE, TSTAT [C], NT [C] int32 nullable.
+ * T, C >= 1; lags >= 0.
+ */
+int csm_xs_regress(csm_ctx* ctx, const double* Y, const double* const* S, int32_t K,
+                   const double* W, int32_t T_m, int64_t N, int32_t standardize, double ridge,
+                   int32_t min_obs, double* GAMMA, double* R2, int32_t* NOBS);
+int csm_newey_west(csm_ctx* ctx, const double* G, int32_t T, int32_t C, int64_t ld, int32_t lags,
+                   double* MEAN, double* SE, double* TSTAT, int32_t* NT);
+
+/*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
  * month-return panel R[T_m][N] (csm_momentum's R; NaN = no row).  src[B][T_m] int32 out: the
  * source months; PMb[T_m][B][N] out: month prices p0 * prod(1 + r) over the resampled months,
