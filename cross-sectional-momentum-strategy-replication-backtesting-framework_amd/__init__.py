@@ -21,17 +21,22 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.next_ret                       residual momentum; the next return of any signal (B1..B6)
   Engine.xs_regress / newey_west        per-month cross-sectional regressions (OLS, WLS, ridge) and
   Engine.fama_macbeth / fama_macbeth    Newey-West t-statistics of any monthly series (R1..R6)
+  Engine.deciles_within / group_stats   qcut inside groups (sector-neutral deciles, dependent sorts)
+  Engine.run_neutral / neutral_momentum and industry-adjusted signals (rules N1..N6)
+  dependent_double_sort                 n1 bins of one signal, n2 bins of another inside each
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyOut, Engine, FamaMacBethOut, MarketModelOut, MonthStats, NeweyWestOut,
+from .engine import (DailyOut, Engine, FamaMacBethOut, GroupStatsOut, MarketModelOut, MonthStats, NeweyWestOut,
                      PipelineOut, PortfolioOut, SignalsOut, XsRegressOut, absent_tensor, is_absent,
                      quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
 from .features import compute_monthly_momentum_from_daily, compute_monthly_turnover, get_engine
-from .lesw import DoubleSortResult, momentum_volume_double_sort
+from .lesw import (DependentSortResult, DoubleSortResult, dependent_double_sort,
+                   momentum_volume_double_sort)
+from .neutral import NeutralResult, group_ids, neutral_momentum
 from .regress import FamaMacBethResult, fama_macbeth
 from .panel import DensePanel, from_long, month_offsets, monthly_frame
 from .replication import (ReplicationResult, assign_deciles_per_date, daily_portfolio_returns,
@@ -49,5 +54,6 @@ __all__ = [
     "assign_deciles_per_date", "monthly_replication", "ensure_dir", "save_plot", "sharpe",
     "DailyOut", "daily_portfolio_returns", "MonthStats", "SignalsOut",
     "MarketModelOut", "XsRegressOut", "NeweyWestOut", "FamaMacBethOut", "FamaMacBethResult",
-    "fama_macbeth",
+    "fama_macbeth", "GroupStatsOut", "DependentSortResult", "dependent_double_sort",
+    "NeutralResult", "group_ids", "neutral_momentum",
 ]

@@ -50,6 +50,8 @@ struct csm_ctx {
   size_t mkt_ws_bytes;    // grown lazily
   void* xs_ws;            // csm_xs_regress's per-slice partial sums and counts, or a series too
   size_t xs_ws_bytes;     // long for csm_newey_west's LDS (xsreg.hip), grown lazily
+  void* grp_ws;           // csm_group_deciles / csm_group_stats: the packed rows, segment offsets
+  size_t grp_ws_bytes;    // and per-group sums (groups.hip), grown lazily
 };
 
 static inline int set_err(csm_ctx* c, int code, const char* fmt, ...) {

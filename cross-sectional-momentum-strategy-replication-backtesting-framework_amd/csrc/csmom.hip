@@ -2540,11 +2540,13 @@ int csm_tune_portfolio(const char* key, int value);  // portfolio.hip
 int csm_tune_ptr_portfolio(const char* key, void* p);  // portfolio.hip
 int csm_tune_signals(const char* key, int value);  // signals.hip
 int csm_tune_market(const char* key, int value);  // market.hip
+int csm_tune_groups(const char* key, int value);  // groups.hip
 
 int csm_tune(const char* key, int value) {
   if (tune_set(g_knobs, key, value) == CSM_OK) return CSM_OK;
   if (csm_tune_signals(key, value) == CSM_OK) return CSM_OK;
   if (csm_tune_market(key, value) == CSM_OK) return CSM_OK;
+  if (csm_tune_groups(key, value) == CSM_OK) return CSM_OK;
   return csm_tune_portfolio(key, value);
 }
 
@@ -2590,8 +2592,9 @@ int csm_create(int device, csm_ctx** out) {
 int csm_destroy(csm_ctx* ctx) {
   if (ctx) (void)csm_allgather_free(ctx);
   if (ctx && (ctx->scratch || ctx->dec_flg || ctx->ticket || ctx->dsplit || ctx->mkt_ws ||
-              ctx->xs_ws)) {
+              ctx->xs_ws || ctx->grp_ws)) {
     (void)hipSetDevice(ctx->device);
+    if (ctx->grp_ws) (void)hipFree(ctx->grp_ws);
     if (ctx->xs_ws) (void)hipFree(ctx->xs_ws);
     if (ctx->mkt_ws) (void)hipFree(ctx->mkt_ws);
     if (ctx->scratch) (void)hipFree(ctx->scratch);

@@ -1,0 +1,567 @@
+// groups.hip -- within-group sorts (rules N1..N6 in DESIGN.md 7): exact qcut labels per (date,
+// group), the groups' and the pooled decile means, and the groups' mean / standard deviation with
+// the adjusted signals.  The work per date is a fixed number of sweeps of the row whatever
+// n_groups is.
+//
+//   k_gpart    N1.  One workgroup per date; each of its GP_WAVES waves owns one contiguous chunk
+//              of the row.  First sweep: per-wave, per-group member counts in LDS (integer adds).
+//              An exclusive prefix over (group, wave) gives the segment offsets SEG[t][g] and each
+//              wave's first slot in each segment.  Second sweep: the members' values and asset
+//              indices go to the packed row SK / SI, group-major and ascending asset inside a
+//              group.  A wave ranks its 64 cells by peeling the groups present in them: the first
+//              unhandled lane's id, the ballot of the lanes that share it, mbcnt for the rank --
+//              as many trips as there are distinct groups in the 64 cells.  Cells outside every
+//              group get their -1 / NaN outputs here.
+//   k_gdec     N2, N3.  One workgroup per (date, group).  The segment's keys are sorted by a
+//              bitonic network on exactly n keys (every exchange moves the smaller key down, an
+//              exchange whose upper index is past n is skipped: the network of the next power of
+//              two with +inf above n).  SMALL: a segment of at most `cap` keys, sorted in LDS.
+//              Otherwise: tiles of `tile` keys sorted in LDS, the exchanges wider than a tile made
+//              in the packed row itself.  Each launch returns at once on the other's segments.
+//              Edges are NumPy's lerp on the sorted keys as deciles.inc computes them, deduped;
+//              a member's label is the count of edges below its value.  Only keys are sorted, so
+//              labels and sums do not depend on which kernel took the segment.  The sums: label
+//              d's wave adds NR over the packed positions lane, lane + 64, ... from 0.0 (0.0
+//              for a position of another label), then the halving tree over the lanes: an order
+//              that depends on the segment's length alone.
+//   k_gpool    N3.  A lane per (date, label) adds the groups' sums and counts, g ascending.
+//   k_gstats   N4, N5.  One workgroup per (date, group): lane sums over positions tid, tid + 256,
+//              ..., the halving tree per wave, the waves in wave order; then the members' adjusted
+//              signals through SI.
+//
+// No floating-point atomic anywhere: two calls give the same bits.
+#include "csm_common.h"
+
+#define GP_THREADS 1024
+#define GP_WAVES (GP_THREADS / 64)
+#define GP_MAXG 256        // n_groups <= 256
+#define GP_U 4             // steps of 64 cells whose loads a wave issues together
+#define GD_TILE 4096       // keys of one LDS sort (32 KiB)
+#define GD_SMALL_THREADS 256
+#define GD_LONG_THREADS 1024
+#define GS_THREADS 256
+
+// segments of at most this many keys take the LDS kernel (csm_tune "gdec_small_cap" lowers it;
+// the other kernel's tile is then twice the next power of two, GD_TILE at most)
+static int g_tune_gdec_small_cap = GD_TILE;
+
+static const TuneKnob g_knobs[] = {
+    {"gdec_small_cap", &g_tune_gdec_small_cap, [](int v) { return v >= 1 && v <= GD_TILE; }},
+};
+
+__device__ __forceinline__ double gwave_tree(double v) {
+#pragma unroll
+  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
+  return v;
+}
+__device__ __forceinline__ int gwave_tree(int v) {
+#pragma unroll
+  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
+  return v;
+}
+
+// ------------------------------------------------------------------------------------ N1
+// the group of cell i of the row, -1 for none
+__device__ __forceinline__ int cell_group(double x, int id, int n_groups) {
+  return (x == x && id >= 0 && id < n_groups) ? id : -1;
+}
+
+__global__ __launch_bounds__(GP_THREADS) void k_gpart(
+    const double* __restrict__ S, const int16_t* __restrict__ GID, int64_t g_ld, int64_t N,
+    int n_groups, int32_t* __restrict__ SEG, uint32_t* __restrict__ SI, double* __restrict__ SK,
+    int8_t* __restrict__ L, int32_t* __restrict__ NVG, int32_t* __restrict__ NV,
+    double* __restrict__ SA, double* __restrict__ SZ, double* __restrict__ SB) {
+  __shared__ int s_cnt[GP_WAVES][GP_MAXG];   // counts, then each wave's next slot per group
+  __shared__ int s_tot[GP_MAXG];
+  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const double* __restrict__ row = S + (int64_t)t * N;
+  const int16_t* __restrict__ gid = GID + (int64_t)t * g_ld;
+  const int64_t per = ((N + GP_THREADS - 1) / GP_THREADS) * 64;   // cells of one wave's chunk
+  const int64_t i0 = (int64_t)wave * per;
+  const int64_t i1 = i0 + per < N ? i0 + per : N;
+  for (int k = tid; k < GP_WAVES * GP_MAXG; k += GP_THREADS) (&s_cnt[0][0])[k] = 0;
+  __syncthreads();
+  for (int64_t b = i0; b < i1; b += 64 * GP_U) {   // GP_U steps of 64 cells, their loads together
+    double xv[GP_U];
+    int gv[GP_U];
+#pragma unroll
+    for (int u = 0; u < GP_U; ++u) {
+      const int64_t i = b + u * 64 + lane;
+      xv[u] = i < i1 ? row[i] : qnan();
+      gv[u] = i < i1 ? (int)gid[i] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < GP_U; ++u) {
+      const int g = cell_group(xv[u], gv[u], n_groups);
+      if (g >= 0) atomicAdd(&s_cnt[wave][g], 1);
+    }
+  }
+  __syncthreads();
+  if (tid < GP_MAXG) {
+    int c = 0;
+    if (tid < n_groups)
+      for (int w = 0; w < GP_WAVES; ++w) c += s_cnt[w][tid];
+    s_tot[tid] = c;
+  }
+  __syncthreads();
+  if (wave == 0) {   // exclusive prefix over the groups, four per lane
+    int v[4], s = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      v[k] = s_tot[4 * lane + k];
+      s += v[k];
+    }
+    int inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int u = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += u;
+    }
+    int off = inc - s;
+    int32_t* seg = SEG + (int64_t)t * (n_groups + 1);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int g = 4 * lane + k;
+      s_tot[g] = off;
+      if (g < n_groups) {
+        seg[g] = off;
+        if (NVG) NVG[(int64_t)t * n_groups + g] = v[k];
+      }
+      off += v[k];
+    }
+    if (lane == 63) {
+      seg[n_groups] = inc;
+      if (NV) NV[t] = inc;
+    }
+  }
+  __syncthreads();
+  if (tid < n_groups) {
+    int run = s_tot[tid];
+    for (int w = 0; w < GP_WAVES; ++w) {
+      const int c = s_cnt[w][tid];
+      s_cnt[w][tid] = run;
+      run += c;
+    }
+  }
+  __syncthreads();
+  uint32_t* __restrict__ si = SI + (int64_t)t * N;
+  double* __restrict__ sk = SK + (int64_t)t * N;
+  const double NaN = qnan();
+  for (int64_t b0 = i0; b0 < i1; b0 += 64 * GP_U) {   // (wave-uniform trips)
+    double xv[GP_U];
+    int gv[GP_U];
+#pragma unroll
+    for (int u = 0; u < GP_U; ++u) {
+      const int64_t i = b0 + u * 64 + lane;
+      xv[u] = i < i1 ? row[i] : NaN;
+      gv[u] = i < i1 ? (int)gid[i] : -1;
+    }
+#pragma unroll
+    for (int u = 0; u < GP_U; ++u) {
+      const int64_t i = b0 + u * 64 + lane;
+      const double x = xv[u];
+      int g = -1;
+      if (i < i1) {
+        g = cell_group(x, gv[u], n_groups);
+        if (g < 0) {
+          if (L) L[(int64_t)t * N + i] = -1;
+          if (SA) SA[(int64_t)t * N + i] = NaN;
+          if (SZ) SZ[(int64_t)t * N + i] = NaN;
+          if (SB) SB[(int64_t)t * N + i] = NaN;
+        }
+      }
+      uint64_t rem = __ballot(g >= 0);
+      while (rem) {   // (wave-uniform)
+        const int leader = __ffsll((unsigned long long)rem) - 1;
+        const int gl = __builtin_amdgcn_readlane(g, leader);
+        const uint64_t m = __ballot(g == gl);
+        if (g == gl) {
+          const int pos = s_cnt[wave][gl] + lane_prefix(m);
+          si[pos] = (uint32_t)i;
+          sk[pos] = x;
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (lane == leader) s_cnt[wave][gl] += __popcll(m);
+        __builtin_amdgcn_wave_barrier();
+        rem &= ~m;
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------ N2
+__device__ __forceinline__ void cmpx(double* a, uint32_t lo, uint32_t hi) {
+  const double x = a[lo], y = a[hi];
+  if (x > y) {
+    a[lo] = y;
+    a[hi] = x;
+  }
+}
+// the first exchange of the merge of width k: lo with lo ^ (k - 1), over a[0..len)
+template <int NT>
+__device__ __forceinline__ void bit_flip(double* a, uint32_t len, uint32_t k) {
+  const uint32_t h = k >> 1;
+  for (uint32_t q = threadIdx.x;; q += NT) {
+    const uint32_t lo = ((q & ~(h - 1)) << 1) | (q & (h - 1));
+    if (lo >= len) break;
+    const uint32_t hi = lo ^ (k - 1);
+    if (hi < len) cmpx(a, lo, hi);
+  }
+}
+// a later exchange of a merge: lo with lo + j
+template <int NT>
+__device__ __forceinline__ void bit_step(double* a, uint32_t len, uint32_t j) {
+  for (uint32_t q = threadIdx.x;; q += NT) {
+    const uint32_t lo = ((q & ~(j - 1)) << 1) | (q & (j - 1));
+    if (lo >= len) break;
+    const uint32_t hi = lo + j;
+    if (hi < len) cmpx(a, lo, hi);
+  }
+}
+// sorts s[0..len) (LDS), len <= GD_TILE
+template <int NT>
+__device__ __forceinline__ void tile_sort(double* s, uint32_t len) {
+  for (uint32_t k = 2; (k >> 1) < len; k <<= 1) {
+    bit_flip<NT>(s, len, k);
+    __syncthreads();
+    for (uint32_t j = k >> 2; j > 0; j >>= 1) {
+      bit_step<NT>(s, len, j);
+      __syncthreads();
+    }
+  }
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_gdec(
+    const double* __restrict__ S, const double* __restrict__ NR, int64_t N, int n_groups,
+    int n_bins, QTab qt, int min_group, int cap, int tile, const int32_t* __restrict__ SEG,
+    const uint32_t* __restrict__ SI, double* SK, int8_t* SL, int8_t* __restrict__ L,
+    double* __restrict__ SUMG, int32_t* __restrict__ CNTG, double* __restrict__ EWG) {
+  constexpr int NT = SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS;
+  __shared__ double s_key[GD_TILE];
+  __shared__ int8_t s_lab[SMALL ? GD_TILE : 16];
+  __shared__ double s_edge[MAXQ], s_bins[MAXQ];
+  __shared__ int s_nb;
+  const int64_t cell = blockIdx.x;
+  const int t = (int)(cell / n_groups), g = (int)(cell % n_groups);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int seg0 = SEG[(int64_t)t * (n_groups + 1) + g];
+  const int n = SEG[(int64_t)t * (n_groups + 1) + g + 1] - seg0;
+  if (SMALL ? n > cap : n <= cap) return;   // the other launch's segment (block-uniform)
+  double* gk = SK + (int64_t)t * N + seg0;   // the segment's keys in the packed row
+  const uint32_t* __restrict__ si = SI + (int64_t)t * N + seg0;
+  const bool ranked = n >= min_group && n > 0;
+  const uint32_t un = (uint32_t)n;
+  if (ranked) {
+    if (SMALL) {
+      for (int p = tid; p < n; p += NT) s_key[p] = gk[p];
+      __syncthreads();
+      tile_sort<NT>(s_key, un);
+    } else {
+      const uint32_t tl = (uint32_t)tile;
+      for (uint32_t tb = 0; tb < un; tb += tl) {
+        const uint32_t len = un - tb < tl ? un - tb : tl;
+        for (uint32_t p = tid; p < len; p += NT) s_key[p] = gk[tb + p];
+        __syncthreads();
+        tile_sort<NT>(s_key, len);
+        for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s_key[p];
+        __syncthreads();
+      }
+      for (uint32_t k = 2 * tl; k != 0 && (k >> 1) < un; k <<= 1) {
+        bit_flip<NT>(gk, un, k);
+        __syncthreads();
+        for (uint32_t j = k >> 2; j >= tl; j >>= 1) {
+          bit_step<NT>(gk, un, j);
+          __syncthreads();
+        }
+        for (uint32_t tb = 0; tb < un; tb += tl) {   // the exchanges narrower than a tile
+          const uint32_t len = un - tb < tl ? un - tb : tl;
+          for (uint32_t p = tid; p < len; p += NT) s_key[p] = gk[tb + p];
+          __syncthreads();
+          for (uint32_t j = tl >> 1; j > 0; j >>= 1) {
+            bit_step<NT>(s_key, len, j);
+            __syncthreads();
+          }
+          for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s_key[p];
+          __syncthreads();
+        }
+      }
+    }
+    // edges: NumPy's lerp on the sorted keys, as deciles.inc
+    const double* srt = SMALL ? s_key : gk;
+    if (tid <= n_bins) {
+      const double v = (double)(n - 1) * qt.q[tid];
+      double ek;
+      if (v >= (double)(n - 1)) {
+        ek = srt[n - 1];
+      } else {
+        const double p = floor(v);
+        const double gm = v - p;
+        const int pi = (int)p;
+        const double a = srt[pi];
+        const double b = (gm != 0.0) ? srt[pi + 1] : a;
+        const double d = b - a;
+        ek = (gm >= 0.5) ? (b - d * (1.0 - gm)) : (a + d * gm);
+      }
+      s_edge[tid] = ek;
+    }
+    __syncthreads();
+    if (tid == 0) {   // duplicates='drop'
+      int nu = 0;
+      const int ne = n_bins + 1;
+      for (int k = 0; k < ne; ++k) {
+        bool seen = false;
+        for (int j = 0; j < nu; ++j) seen |= s_bins[j] == s_edge[k];
+        if (!seen) s_bins[nu++] = s_edge[k];
+      }
+      if (!(nu < ne && ne != 2)) {
+        for (int k = 0; k < ne; ++k) s_bins[k] = s_edge[k];
+        nu = ne;
+      }
+      s_nb = nu;
+    }
+  } else if (tid == 0) {
+    s_nb = 0;
+  }
+  __syncthreads();
+  // labels; with NR each position's label and next return are staged where the keys were
+  const int nb = s_nb;
+  double* rr = SMALL ? s_key : gk;
+  int8_t* lb = SMALL ? s_lab : SL + (int64_t)t * N + seg0;
+  for (int p = tid; p < n; p += NT) {
+    const int64_t idx = (int64_t)t * N + si[p];
+    const double x = SMALL ? gk[p] : S[idx];   // (the LDS kernel leaves the packed keys unsorted)
+    int ids = 0;
+    for (int j = 0; j < nb; ++j) ids += (s_bins[j] < x) ? 1 : 0;
+    if (nb > 0 && x == s_bins[0]) ids = 1;
+    const int lab = (nb == 0 || ids == 0 || ids == nb) ? -1 : ids - 1;
+    L[idx] = (int8_t)lab;
+    if (NR) {
+      const double r = NR[idx];
+      const bool ok = lab >= 0 && r == r;
+      rr[p] = ok ? r : 0.0;
+      lb[p] = (int8_t)(ok ? lab : -1);
+    }
+  }
+  if (!NR) return;
+  __syncthreads();
+  for (int d = wave; d < n_bins; d += NT / 64) {   // (wave-uniform)
+    double s = 0.0;
+    int c = 0;
+    for (int p = lane; p < n; p += 64) {
+      const bool h = lb[p] == d;
+      s = s + (h ? rr[p] : 0.0);
+      c += h ? 1 : 0;
+    }
+    s = gwave_tree(s);
+    c = gwave_tree(c);
+    if (lane == 0) {
+      const int64_t o = cell * n_bins + d;
+      SUMG[o] = s;
+      CNTG[o] = c;
+      if (EWG) EWG[o] = c > 0 ? s / (double)c : qnan();
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------ N3
+__global__ __launch_bounds__(64) void k_gpool(const double* __restrict__ SUMG,
+                                              const int32_t* __restrict__ CNTG, int T_m,
+                                              int n_groups, int n_bins, double* __restrict__ EW,
+                                              int32_t* __restrict__ CNT) {
+  const int64_t id = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (id >= (int64_t)T_m * n_bins) return;
+  const int64_t t = id / n_bins;
+  const int d = (int)(id % n_bins);
+  double s = 0.0;
+  int c = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    const int64_t o = (t * n_groups + g) * n_bins + d;
+    s = s + SUMG[o];
+    c += CNTG[o];
+  }
+  if (EW) EW[id] = c > 0 ? s / (double)c : qnan();
+  if (CNT) CNT[id] = c;
+}
+
+// -------------------------------------------------------------------------------- N4, N5
+// lane sums -> one sum: the tree per wave, the waves in wave order from 0.0
+__device__ __forceinline__ double gs_block_sum(double v, double* s_part) {
+  const int tid = threadIdx.x;
+  v = gwave_tree(v);
+  __syncthreads();   // s_part's last readers are done
+  if ((tid & 63) == 0) s_part[tid >> 6] = v;
+  __syncthreads();
+  double r = 0.0;
+#pragma unroll
+  for (int w = 0; w < GS_THREADS / 64; ++w) r = r + s_part[w];
+  return r;
+}
+
+__global__ __launch_bounds__(GS_THREADS) void k_gstats(
+    int64_t N, int n_groups, const int32_t* __restrict__ SEG, const uint32_t* __restrict__ SI,
+    const double* __restrict__ SK, double* __restrict__ GMEAN, double* __restrict__ GSD,
+    int32_t* __restrict__ GCNT, double* __restrict__ SA, double* __restrict__ SZ,
+    double* __restrict__ SB) {
+  __shared__ double s_part[GS_THREADS / 64];
+  const int64_t cell = blockIdx.x;
+  const int t = (int)(cell / n_groups), g = (int)(cell % n_groups);
+  const int tid = threadIdx.x;
+  const int seg0 = SEG[(int64_t)t * (n_groups + 1) + g];
+  const int n = SEG[(int64_t)t * (n_groups + 1) + g + 1] - seg0;
+  const double* __restrict__ sk = SK + (int64_t)t * N + seg0;
+  const uint32_t* __restrict__ si = SI + (int64_t)t * N + seg0;
+  double a = 0.0;
+  for (int p = tid; p < n; p += GS_THREADS) a = a + sk[p];
+  const double sum = gs_block_sum(a, s_part);
+  const double mean = n > 0 ? sum / (double)n : qnan();
+  double q = 0.0;
+  for (int p = tid; p < n; p += GS_THREADS) {
+    const double d = sk[p] - mean;
+    q = q + d * d;
+  }
+  const double ss = gs_block_sum(q, s_part);
+  const double sd = n >= 2 ? sqrt(ss / (double)(n - 1)) : qnan();
+  if (tid == 0) {
+    if (GMEAN) GMEAN[cell] = mean;
+    if (GSD) GSD[cell] = sd;
+    if (GCNT) GCNT[cell] = n;
+  }
+  if (!SA && !SZ && !SB) return;
+  const bool zok = sd == sd && sd != 0.0;
+  for (int p = tid; p < n; p += GS_THREADS) {
+    const int64_t idx = (int64_t)t * N + si[p];
+    const double sa = sk[p] - mean;
+    if (SA) SA[idx] = sa;
+    if (SZ) SZ[idx] = zok ? sa / sd : qnan();
+    if (SB) SB[idx] = mean;
+  }
+}
+
+// ----------------------------------------------------------------------------------- host
+struct GrpWs {
+  int32_t* seg;    // [T_m][n_groups + 1] segment offsets in the packed row
+  uint32_t* si;    // [T_m][N] the members' asset indices, group-major
+  double* sk;      // [T_m][N] their values (k_gdec: sorted keys, then staged next returns)
+  int8_t* sl;      // [T_m][N] k_gdec's staged labels (segments past the LDS cap)
+  double* sumg;    // [T_m][n_groups][n_bins]
+  int32_t* cntg;   // [T_m][n_groups][n_bins]
+};
+
+static inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+static int grp_reserve(csm_ctx* ctx, const char* who, int32_t T_m, int64_t N, int32_t n_groups,
+                       int32_t n_bins, GrpWs* w) {
+  const size_t cells = (size_t)T_m * (size_t)N, tg = (size_t)T_m * (size_t)n_groups;
+  const size_t b_seg = up16(((size_t)T_m * (size_t)(n_groups + 1)) * sizeof(int32_t));
+  const size_t b_si = up16(cells * sizeof(uint32_t)), b_sk = up16(cells * sizeof(double));
+  const size_t b_sl = up16(cells), b_sum = up16(tg * (size_t)n_bins * sizeof(double));
+  const size_t b_cnt = up16(tg * (size_t)n_bins * sizeof(int32_t));
+  int r = ctx_reserve(ctx, who, "the group partition workspace", &ctx->grp_ws, &ctx->grp_ws_bytes,
+                      b_seg + b_si + b_sk + b_sl + b_sum + b_cnt);
+  if (r) return r;
+  char* p = (char*)ctx->grp_ws;
+  w->sk = (double*)p;
+  p += b_sk;
+  w->sumg = (double*)p;
+  p += b_sum;
+  w->si = (uint32_t*)p;
+  p += b_si;
+  w->seg = (int32_t*)p;
+  p += b_seg;
+  w->cntg = (int32_t*)p;
+  p += b_cnt;
+  w->sl = (int8_t*)p;
+  return CSM_OK;
+}
+
+// the checks the two entry points share
+static int grp_check(csm_ctx* ctx, const char* who, const double* S, const int16_t* GID,
+                     int64_t g_ld, int32_t T_m, int64_t N, int32_t n_groups) {
+  if (!S || !GID || T_m < 1 || N < 1 || N > 0x7FFFFFFFLL || (int64_t)T_m > ((int64_t)1 << 40) / N)
+    return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld)", who, T_m, (long long)N);
+  if (n_groups < 1 || n_groups > GP_MAXG)
+    return set_err(ctx, CSM_E_INVAL, "%s: n_groups=%d is outside [1, %d]", who, n_groups, GP_MAXG);
+  if (g_ld != 0 && g_ld != N)
+    return set_err(ctx, CSM_E_INVAL, "%s: g_ld=%lld must be 0 (one static row) or N=%lld", who,
+                   (long long)g_ld, (long long)N);
+  if ((int64_t)T_m * n_groups > 0x7FFFFFFFLL)
+    return set_err(ctx, CSM_E_INVAL, "%s: T_m * n_groups = %lld segments exceed one launch", who,
+                   (long long)T_m * n_groups);
+  return CSM_OK;
+}
+
+extern "C" {
+
+int csm_tune_groups(const char* key, int value) { return tune_set(g_knobs, key, value); }
+
+int csm_group_deciles(csm_ctx* ctx, const double* S, const double* NR, const int16_t* GID,
+                      int64_t g_ld, int32_t T_m, int64_t N, int32_t n_groups, int32_t n_bins,
+                      const double* qtable, int32_t min_group, int8_t* L, double* EW, int32_t* CNT,
+                      int32_t* NV, double* EWG, int32_t* CNTG, int32_t* NVG) {
+  const char* who = "csm_group_deciles";
+  int r = prep(ctx);
+  if (r) return r;
+  r = grp_check(ctx, who, S, GID, g_ld, T_m, N, n_groups);
+  if (r) return r;
+  if (!L || !qtable) return set_err(ctx, CSM_E_INVAL, "%s: L or qtable is NULL", who);
+  if (min_group < 1)
+    return set_err(ctx, CSM_E_INVAL, "%s: min_group=%d must be at least 1", who, min_group);
+  if (n_bins < 1 || n_bins > MAXQ - 1)
+    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d is outside [1, %d]", who, n_bins, MAXQ - 1);
+  if (NR && !nb_dispatch<2, 3, 4, 5, 10, 20>(n_bins, [](auto) {}))
+    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", who,
+                   n_bins);
+  GrpWs w;
+  r = grp_reserve(ctx, who, T_m, N, n_groups, n_bins, &w);
+  if (r) return r;
+  QTab q{};
+  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
+  const int cap = g_tune_gdec_small_cap;
+  int tile = 2;
+  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  hipLaunchKernelGGL(k_gpart, dim3((unsigned)T_m), dim3(GP_THREADS), 0, ctx->stream, S, GID, g_ld,
+                     N, n_groups, w.seg, w.si, w.sk, L, NVG, NV, (double*)nullptr,
+                     (double*)nullptr, (double*)nullptr);
+  LAUNCH_CHECK(ctx, "k_gpart");
+  const unsigned segs = (unsigned)((int64_t)T_m * n_groups);
+  int32_t* cntg = CNTG ? CNTG : w.cntg;
+  hipLaunchKernelGGL(k_gdec<true>, dim3(segs), dim3(GD_SMALL_THREADS), 0, ctx->stream, S, NR, N,
+                     n_groups, n_bins, q, min_group, cap, tile, w.seg, w.si, w.sk, w.sl, L, w.sumg,
+                     cntg, EWG);
+  LAUNCH_CHECK(ctx, "k_gdec (LDS)");
+  hipLaunchKernelGGL(k_gdec<false>, dim3(segs), dim3(GD_LONG_THREADS), 0, ctx->stream, S, NR, N,
+                     n_groups, n_bins, q, min_group, cap, tile, w.seg, w.si, w.sk, w.sl, L, w.sumg,
+                     cntg, EWG);
+  LAUNCH_CHECK(ctx, "k_gdec (tiled)");
+  if (NR && (EW || CNT)) {
+    const int64_t lanes = (int64_t)T_m * n_bins;
+    hipLaunchKernelGGL(k_gpool, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, ctx->stream,
+                       w.sumg, cntg, T_m, n_groups, n_bins, EW, CNT);
+    LAUNCH_CHECK(ctx, "k_gpool");
+  }
+  return CSM_OK;
+}
+
+int csm_group_stats(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g_ld, int32_t T_m,
+                    int64_t N, int32_t n_groups, double* GMEAN, double* GSD, int32_t* GCNT,
+                    double* SA, double* SZ, double* SB) {
+  const char* who = "csm_group_stats";
+  int r = prep(ctx);
+  if (r) return r;
+  r = grp_check(ctx, who, S, GID, g_ld, T_m, N, n_groups);
+  if (r) return r;
+  GrpWs w;
+  r = grp_reserve(ctx, who, T_m, N, n_groups, 1, &w);
+  if (r) return r;
+  hipLaunchKernelGGL(k_gpart, dim3((unsigned)T_m), dim3(GP_THREADS), 0, ctx->stream, S, GID, g_ld,
+                     N, n_groups, w.seg, w.si, w.sk, (int8_t*)nullptr, (int32_t*)nullptr,
+                     (int32_t*)nullptr, SA, SZ, SB);
+  LAUNCH_CHECK(ctx, "k_gpart");
+  hipLaunchKernelGGL(k_gstats, dim3((unsigned)((int64_t)T_m * n_groups)), dim3(GS_THREADS), 0,
+                     ctx->stream, N, n_groups, w.seg, w.si, w.sk, GMEAN, GSD, GCNT, SA, SZ, SB);
+  LAUNCH_CHECK(ctx, "k_gstats");
+  return CSM_OK;
+}
+
+}  // extern "C"

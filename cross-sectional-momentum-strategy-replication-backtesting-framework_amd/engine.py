@@ -153,6 +153,17 @@ class FamaMacBethOut(XsRegressOut):
 
 
 @dataclass
+class GroupStatsOut:
+    """csm_group_stats (rules N4, N5); None = not asked for."""
+    GMEAN: torch.Tensor | None = None    # [T_m][n_groups] mean of the signal over the group's members
+    GSD: torch.Tensor | None = None      # [T_m][n_groups] its standard deviation, n - 1 (NaN for n < 2)
+    GCNT: torch.Tensor | None = None     # [T_m][n_groups] int32, the members
+    SA: torch.Tensor | None = None       # [T_m][N] signal minus its group's mean
+    SZ: torch.Tensor | None = None       # [T_m][N] SA over the group's deviation
+    SB: torch.Tensor | None = None       # [T_m][N] the group's mean at its members: the industry signal
+
+
+@dataclass
 class ShardState:
     """signal_shard's end-state record [5][N] (present months, pending ranked row, its
     subset-ffilled price, first / last present month) with the daily panel it came from
@@ -974,6 +985,99 @@ class Engine:
         r2 = self.newey_west(r.R2, lags)
         return FamaMacBethOut(GAMMA=r.GAMMA, R2=r.R2, NOBS=r.NOBS, MEAN=nw.MEAN, SE=nw.SE, T=nw.T,
                               NT=nw.NT, R2_MEAN=r2.MEAN, lags=lags)
+
+    # ------------------------------------------------------------------ within-group sorts
+    def _group_ids(self, GID, T_m, N):
+        """GID as csm_group_* takes it: int16 [T_m][N] (one row per month) or [N] (static);
+        returns (GID, g_ld)."""
+        if not isinstance(GID, torch.Tensor) or GID.dtype != torch.int16:
+            raise TypeError("GID must be an int16 torch tensor (labels: L.to(torch.int16))")
+        if GID.dim() == 1:
+            _need(GID, "GID", torch.int16, (N,), self.device)
+            return GID, 0
+        _need(GID, "GID", torch.int16, (T_m, N), self.device)
+        return GID, N
+
+    def deciles_within(self, S, NR, GID, n_groups, n_bins=10, min_group=1, with_groups=False,
+                       with_nv=False):
+        """csm_group_deciles (rules N1..N3): the qcut labels of S inside each group of each date
+        -- sector-neutral deciles; with a first sort's labels as GID the dependent double sort --
+        and, with NR, the pooled decile means.  GID: int16 [T_m][N] or a static [N]; an id outside
+        [0, n_groups) means no group; a group with fewer than min_group members is not ranked.
+        Returns (L, EW, CNT[, NV][, EWG, CNTG, NVG]); EW / CNT / EWG / CNTG are None without NR."""
+        T_m, N = S.shape
+        _need(S, "S", torch.float64, (T_m, N), self.device)
+        if NR is not None:
+            _need(NR, "NR", torch.float64, (T_m, N), self.device)
+        GID, g_ld = self._group_ids(GID, T_m, N)
+        G, nb = int(n_groups), int(n_bins)
+        L = self.empty((T_m, N), torch.int8)
+        EW = self.empty((T_m, nb)) if NR is not None else None
+        CNT = self.empty((T_m, nb), torch.int32) if NR is not None else None
+        NV = self.empty((T_m,), torch.int32) if with_nv else None
+        grp = with_groups and NR is not None and G >= 1
+        EWG = self.empty((T_m, G, nb)) if grp else None
+        CNTG = self.empty((T_m, G, nb), torch.int32) if grp else None
+        NVG = self.empty((T_m, max(G, 1)), torch.int32) if with_groups else None
+        q = quantile_table(nb) if nb >= 1 else np.zeros(1)
+        self._call("csm_group_deciles", _ptr(S), _ptr(NR), _ptr(GID), g_ld, T_m, N, G, nb,
+                   q.ctypes.data_as(ctypes.c_void_p), int(min_group), _ptr(L), _ptr(EW), _ptr(CNT),
+                   _ptr(NV), _ptr(EWG), _ptr(CNTG), _ptr(NVG))
+        out = (L, EW, CNT)
+        if with_nv:
+            out += (NV,)
+        if with_groups:
+            out += (EWG, CNTG, NVG)
+        return out
+
+    GROUP_OUTPUTS = ("GMEAN", "GSD", "GCNT", "SA", "SZ", "SB")
+
+    def group_stats(self, S, GID, n_groups, outputs=None) -> GroupStatsOut:
+        """csm_group_stats (rules N4, N5): each group's mean, standard deviation and member count
+        per date, and per member the demeaned signal SA, the z-score SZ and the group's mean SB.
+        outputs: the GroupStatsOut fields to compute (default: all)."""
+        T_m, N = S.shape
+        _need(S, "S", torch.float64, (T_m, N), self.device)
+        GID, g_ld = self._group_ids(GID, T_m, N)
+        outputs = self.GROUP_OUTPUTS if outputs is None else tuple(outputs)
+        unknown = set(outputs) - set(self.GROUP_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        G = int(n_groups)
+        o = {k: self.empty((T_m, max(G, 1)) if k[0] == "G" else (T_m, N),
+                           torch.int32 if k == "GCNT" else torch.float64) for k in outputs}
+        self._call("csm_group_stats", _ptr(S), _ptr(GID), g_ld, T_m, N, G,
+                   *(_ptr(o.get(k)) for k in self.GROUP_OUTPUTS))
+        return GroupStatsOut(**o)
+
+    def run_neutral(self, P, month_start, GID, n_groups, signal="mom", adjust=None, J=12, skip=1,
+                    n_bins=10, min_group=1, window=12, min_obs=None) -> PipelineOut:
+        """One full pass ranked inside groups (Moskowitz-Grinblatt 1999).  The signal is built as
+        run (signal "mom") or run_signal (its names) build it.  adjust None: labels by
+        deciles_within, the decile means pooled over the groups.  adjust "demean" / "zscore": the
+        signal minus its group's mean (over its deviation), rule N5, then a plain deciles on it.
+        M is the signal ranked and NR the signal's next return (rule N6)."""
+        if adjust not in (None, "demean", "zscore"):
+            raise ValueError(f"adjust must be None, 'demean' or 'zscore', got {adjust!r}")
+        if signal == "mom":
+            PM, _ = self.month_end(P, month_start)
+            T_m, N = PM.shape
+            if self.default_chunks(T_m, N, J, skip) > 1:
+                _, S, NR = self.momentum_chunked(PM, J, skip)
+            else:
+                _, S, NR = self.momentum(PM, J, skip)
+        else:
+            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs)
+            PM, S, NR = r.PM, r.M, r.NR
+        if adjust is None:
+            L, EW, CNT, NV = self.deciles_within(S, NR, GID, n_groups, n_bins, min_group,
+                                                 with_nv=True)
+        else:
+            field = "SA" if adjust == "demean" else "SZ"
+            S = getattr(self.group_stats(S, GID, n_groups, outputs=(field,)), field)
+            L, EW, CNT, NV = self.deciles(S, NR, n_bins, with_nv=True)
+        LS = self.long_short(EW, CNT)
+        return PipelineOut(PM=PM, M=S, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, NV=NV)
 
     def turnover_features(self, PM, VOL, so, mcap, lookback=3):
         """csm_turnover_features (src/features.py:60-107, rule T1): (ADV, SH, TURN, TAVG)."""

@@ -40,4 +40,28 @@ def momentum_volume_double_sort(eng, PM, VOL, M, NR, so, mcap, n_mom=10, n_vol=3
     return DoubleSortResult(Lm=Lm, Lv=Lv, Lc=Lc, PR=PR, LS=LS, TAVG=TAVG)
 
 
-__all__ = ["DoubleSortResult", "momentum_volume_double_sort"]
+@dataclass
+class DependentSortResult:
+    Lm: torch.Tensor          # [T_m][N] first sort's label (n1 bins of S1)
+    Lv: torch.Tensor          # [T_m][N] second sort's label: n2 bins of S2 inside each first bin
+    Lc: torch.Tensor          # [T_m][N] cell = n2 * Lm + Lv
+    PR: torch.Tensor          # [T_m][n1][n2] cell returns (K-overlapped)
+    LS: torch.Tensor          # [T_m][n1] top minus bottom second-sort bin per first bin
+
+
+def dependent_double_sort(eng, S1, S2, NR, n1=3, n2=10, K=1, W=None) -> DependentSortResult:
+    """The conditional double sort: n1 bins of S1 per date, then n2 bins of S2 inside each of
+    them (csm_group_deciles with the first labels as the groups, rules N1, N2), and the
+    n1 * n2 cell portfolios held K months."""
+    T_m, N = S1.shape
+    L1, _, _, _ = eng.deciles(S1, None, n1)
+    L2, _, _ = eng.deciles_within(S2, None, L1.to(torch.int16), n1, n2)
+    Lc = eng.combine_labels(L1, L2, n2)
+    out = eng.portfolio(Lc, NR, n1 * n2, K=K, W=W, with_costs=False)
+    PR = out.PR[:, 0, :].reshape(T_m, n1, n2)
+    LS = PR[:, :, n2 - 1] - PR[:, :, 0]
+    return DependentSortResult(Lm=L1, Lv=L2, Lc=Lc, PR=PR, LS=LS)
+
+
+__all__ = ["DoubleSortResult", "DependentSortResult", "dependent_double_sort",
+           "momentum_volume_double_sort"]

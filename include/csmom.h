@@ -756,6 +756,55 @@ int csm_newey_west(csm_ctx* ctx, const double* G, int32_t T, int32_t C, int64_t 
                    double* MEAN, double* SE, double* TSTAT, int32_t* NT);
 
 /*
+ * Within-group sorts (rules N1..N6 in DESIGN.md section 7): the reference's
+ * groupby(['date', 'group'])['mom_J'].transform(assign_deciles_per_date) -- sector-neutral deciles
+ * (Moskowitz-Grinblatt 1999), and with a first sort's labels as the groups the dependent double
+ * sort -- and the groups' statistics with the industry-adjusted signals.  The cost per date is a
+ * fixed number of sweeps of the row, whatever n_groups is.
+ *   S [T_m][N] the signal (NaN, the ABSENT payload included: not ranked);  GID int16, row t at
+ *   GID + t * g_ld: g_ld = N one row per month, g_ld = 0 one static row;  1 <= n_groups <= 256.
+ *   N1  cell (t, a) is a member of group g = GID[t * g_ld + a] iff 0 <= g < n_groups and S[t][a]
+ *       is not NaN; any other id means no group (ids are device data: never an error).
+ *   N2  L [T_m][N] int8 out: per (t, g) csm_deciles's rule (qtable, n_bins as there: 1..20 without
+ *       NR, 2/3/4/5/10/20 with) on the members' values alone; -1 outside every group and for every
+ *       member of a group with fewer than min_group (>= 1) members at t.  A group of one value or
+ *       of equal values is all -1; two distinct values get 0 and n_bins - 1.
+ *   N3  with NR [T_m][N] (nullable): SUMG[t][g][d] = the sum of NR over the members of (t, g) with
+ *       label d and a non-NaN NR, CNTG their count.  The members of a segment stand in asset
+ *       order at positions 0..n-1; lane l of 64 adds positions l, l + 64, ... from 0.0 (0.0 for a
+ *       position of another label), the lanes by a halving tree (h = 32..1: element j < h +=
+ *       element j + h): a function of the group's size alone.  EWG [T_m][n_groups][n_bins] = SUMG
+ *       / CNTG (NaN where empty); EW [T_m][n_bins] = (SUMG added over g ascending from 0.0) /
+ *       (CNTG added over g) = CNT; NV [T_m] the members of the date, NVG [T_m][n_groups] of the
+ *       group, labelled or not.  EW, CNT, NV, EWG, CNTG, NVG nullable; csm_long_short on EW / CNT
+ *       gives the neutral long-short.
+ *   N6  NR is the caller's: the next return of S itself (csm_signal, csm_next_ret) is the right
+ *       one -- the reference computes next_ret on the rows with a valid signal and drops the rows
+ *       without a decile afterwards (run_demo.py:41-49), so cells without a group simply drop out
+ *       of the means.
+ * "gdec_small_cap" (csm_tune, 1..4096) moves the segment length at which the LDS sort hands over
+ * to the tiled one; labels, counts and sums do not depend on it.
+ *
+ * csm_group_stats: N4  GCNT [T_m][n_groups] int32 the member count n; GMEAN = (sum of S over the
+ *       members) / n, NaN for n = 0: lane l of 256 adds positions l, l + 256, ... from 0.0, each
+ *       wave by the halving tree, the four wave sums in order from 0.0;  GSD = sqrt((sum of
+ *       (s - GMEAN)^2, the same order) / (n - 1)), NaN for n < 2.
+ *   N5  per member cell SA = S - GMEAN, SZ = SA / GSD (NaN where GSD is NaN or 0), SB = GMEAN;
+ *       NaN in every other cell.  GMEAN, GSD, GCNT, SA, SZ, SB nullable: only those given are
+ *       written.
+ * CSM_E_INVAL: n_groups outside [1, 256], g_ld not 0 or N, min_group < 1, a NULL S / GID / L /
+ * qtable, an n_bins csm_deciles refuses, T_m < 1, N < 1 or N >= 2^31, T_m * N > 2^40.  Scratch
+ * (13 B per cell) is the context's.
+ */
+int csm_group_deciles(csm_ctx* ctx, const double* S, const double* NR, const int16_t* GID,
+                      int64_t g_ld, int32_t T_m, int64_t N, int32_t n_groups, int32_t n_bins,
+                      const double* qtable, int32_t min_group, int8_t* L, double* EW, int32_t* CNT,
+                      int32_t* NV, double* EWG, int32_t* CNTG, int32_t* NVG);
+int csm_group_stats(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g_ld, int32_t T_m,
+                    int64_t N, int32_t n_groups, double* GMEAN, double* GSD, int32_t* GCNT,
+                    double* SA, double* SZ, double* SB);
+
+/*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
  * month-return panel R[T_m][N] (csm_momentum's R; NaN = no row).  src[B][T_m] int32 out: the
  * source months; PMb[T_m][B][N] out: month prices p0 * prod(1 + r) over the resampled months,
