@@ -24,20 +24,23 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.deciles_within / group_stats   qcut inside groups (sector-neutral deciles, dependent sorts)
   Engine.run_neutral / neutral_momentum and industry-adjusted signals (rules N1..N6)
   dependent_double_sort                 n1 bins of one signal, n2 bins of another inside each
+  Engine.xs_rank / rank_ic / ic_decay   cross-sectional ranks, per-month Spearman and Pearson ICs
+  information_coefficient               and their decay over horizons (rules I1..I6)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyOut, Engine, FamaMacBethOut, GroupStatsOut, MarketModelOut, MonthStats, NeweyWestOut,
-                     PipelineOut, PortfolioOut, SignalsOut, XsRegressOut, absent_tensor, is_absent,
-                     quantile_table)
+from .engine import (DailyOut, Engine, FamaMacBethOut, GroupStatsOut, ICDecayOut, MarketModelOut,
+                     MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RankICOut, SignalsOut,
+                     XsRegressOut, absent_tensor, is_absent, quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
 from .features import compute_monthly_momentum_from_daily, compute_monthly_turnover, get_engine
 from .lesw import (DependentSortResult, DoubleSortResult, dependent_double_sort,
                    momentum_volume_double_sort)
 from .neutral import NeutralResult, group_ids, neutral_momentum
 from .regress import FamaMacBethResult, fama_macbeth
+from .ic import ICResult, information_coefficient
 from .panel import DensePanel, from_long, month_offsets, monthly_frame
 from .replication import (ReplicationResult, assign_deciles_per_date, daily_portfolio_returns,
                           monthly_replication)
@@ -56,4 +59,5 @@ __all__ = [
     "MarketModelOut", "XsRegressOut", "NeweyWestOut", "FamaMacBethOut", "FamaMacBethResult",
     "fama_macbeth", "GroupStatsOut", "DependentSortResult", "dependent_double_sort",
     "NeutralResult", "group_ids", "neutral_momentum",
+    "RankICOut", "ICDecayOut", "ICResult", "information_coefficient",
 ]

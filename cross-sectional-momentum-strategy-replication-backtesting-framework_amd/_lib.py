@@ -106,6 +106,8 @@ SIGNATURES = {
                                          _p, _p, _p, _p, _p, _p]),
     "csm_group_stats": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p, _p,
                                        _p]),
+    "csm_xs_rank": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i64, _i32, _i32, _i32, _p, _p]),
+    "csm_rank_ic": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
     "csm_bootstrap": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64,
                                      _f64, _p, _p]),
     "csm_boot_scan": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64, _f64,

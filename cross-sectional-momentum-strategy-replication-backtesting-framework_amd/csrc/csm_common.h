@@ -51,7 +51,8 @@ struct csm_ctx {
   void* xs_ws;            // csm_xs_regress's per-slice partial sums and counts, or a series too
   size_t xs_ws_bytes;     // long for csm_newey_west's LDS (xsreg.hip), grown lazily
   void* grp_ws;           // csm_group_deciles / csm_group_stats: the packed rows, segment offsets
-  size_t grp_ws_bytes;    // and per-group sums (groups.hip), grown lazily
+  size_t grp_ws_bytes;    // and per-group sums; csm_xs_rank's the same, csm_rank_ic's index list
+                          // and key rows (groups.hip), grown lazily
 };
 
 static inline int set_err(csm_ctx* c, int code, const char* fmt, ...) {

@@ -29,6 +29,19 @@
 //              ..., the halving tree per wave, the waves in wave order; then the members' adjusted
 //              signals through SI.
 //
+// Ranks and information coefficients (rules I1..I6) stand on the same partition and sort:
+//   k_rank     I1, I2.  One workgroup per (date, group), k_gpart's segments (a NULL GID: one group
+//              of every non-NaN cell).  The keys are sorted as k_gdec sorts them; a member's lt /
+//              le are a lower- and an upper-bound search in the sorted keys, its rank goes out
+//              through SI.  Non-members got their NaN from k_gpart.
+//   k_icpart   I3.  One workgroup per month: the assets with S[t] and Y[t + lead] both not NaN,
+//              in asset order, to an index list and two packed value rows.
+//   k_icpearson I5.  k_gstats's sums on the packed values: the means, then the three centred sums.
+//   k_ic       I4.  One workgroup per month.  LDS: S's keys sorted, each position's centred
+//              doubled rank kept as int32, then Y's keys sorted in the same buffer.  Past the cap
+//              both packed rows are sorted in place and the values re-read through the index
+//              list.  The three sums are int64: exact in any order.
+//
 // No floating-point atomic anywhere: two calls give the same bits.
 #include "csm_common.h"
 
@@ -75,7 +88,8 @@ __global__ __launch_bounds__(GP_THREADS) void k_gpart(
   __shared__ int s_tot[GP_MAXG];
   const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const double* __restrict__ row = S + (int64_t)t * N;
-  const int16_t* __restrict__ gid = GID + (int64_t)t * g_ld;
+  // (GID NULL: csm_xs_rank's one group of every non-NaN cell)
+  const int16_t* __restrict__ gid = GID ? GID + (int64_t)t * g_ld : nullptr;
   const int64_t per = ((N + GP_THREADS - 1) / GP_THREADS) * 64;   // cells of one wave's chunk
   const int64_t i0 = (int64_t)wave * per;
   const int64_t i1 = i0 + per < N ? i0 + per : N;
@@ -88,7 +102,7 @@ __global__ __launch_bounds__(GP_THREADS) void k_gpart(
     for (int u = 0; u < GP_U; ++u) {
       const int64_t i = b + u * 64 + lane;
       xv[u] = i < i1 ? row[i] : qnan();
-      gv[u] = i < i1 ? (int)gid[i] : -1;
+      gv[u] = i < i1 ? (gid ? (int)gid[i] : 0) : -1;
     }
 #pragma unroll
     for (int u = 0; u < GP_U; ++u) {
@@ -154,7 +168,7 @@ __global__ __launch_bounds__(GP_THREADS) void k_gpart(
     for (int u = 0; u < GP_U; ++u) {
       const int64_t i = b0 + u * 64 + lane;
       xv[u] = i < i1 ? row[i] : NaN;
-      gv[u] = i < i1 ? (int)gid[i] : -1;
+      gv[u] = i < i1 ? (gid ? (int)gid[i] : 0) : -1;
     }
 #pragma unroll
     for (int u = 0; u < GP_U; ++u) {
@@ -231,6 +245,40 @@ __device__ __forceinline__ void tile_sort(double* s, uint32_t len) {
   }
 }
 
+// sorts gk[0..un) (the packed row), un past the LDS cap: tiles of tl keys sorted in s (LDS), the
+// exchanges wider than a tile made in gk itself
+template <int NT>
+__device__ __forceinline__ void seg_sort(double* gk, double* s, uint32_t un, uint32_t tl) {
+  const uint32_t tid = threadIdx.x;
+  for (uint32_t tb = 0; tb < un; tb += tl) {
+    const uint32_t len = un - tb < tl ? un - tb : tl;
+    for (uint32_t p = tid; p < len; p += NT) s[p] = gk[tb + p];
+    __syncthreads();
+    tile_sort<NT>(s, len);
+    for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s[p];
+    __syncthreads();
+  }
+  for (uint32_t k = 2 * tl; k != 0 && (k >> 1) < un; k <<= 1) {
+    bit_flip<NT>(gk, un, k);
+    __syncthreads();
+    for (uint32_t j = k >> 2; j >= tl; j >>= 1) {
+      bit_step<NT>(gk, un, j);
+      __syncthreads();
+    }
+    for (uint32_t tb = 0; tb < un; tb += tl) {   // the exchanges narrower than a tile
+      const uint32_t len = un - tb < tl ? un - tb : tl;
+      for (uint32_t p = tid; p < len; p += NT) s[p] = gk[tb + p];
+      __syncthreads();
+      for (uint32_t j = tl >> 1; j > 0; j >>= 1) {
+        bit_step<NT>(s, len, j);
+        __syncthreads();
+      }
+      for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s[p];
+      __syncthreads();
+    }
+  }
+}
+
 template <bool SMALL>
 __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_gdec(
     const double* __restrict__ S, const double* __restrict__ NR, int64_t N, int n_groups,
@@ -258,34 +306,7 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
       __syncthreads();
       tile_sort<NT>(s_key, un);
     } else {
-      const uint32_t tl = (uint32_t)tile;
-      for (uint32_t tb = 0; tb < un; tb += tl) {
-        const uint32_t len = un - tb < tl ? un - tb : tl;
-        for (uint32_t p = tid; p < len; p += NT) s_key[p] = gk[tb + p];
-        __syncthreads();
-        tile_sort<NT>(s_key, len);
-        for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s_key[p];
-        __syncthreads();
-      }
-      for (uint32_t k = 2 * tl; k != 0 && (k >> 1) < un; k <<= 1) {
-        bit_flip<NT>(gk, un, k);
-        __syncthreads();
-        for (uint32_t j = k >> 2; j >= tl; j >>= 1) {
-          bit_step<NT>(gk, un, j);
-          __syncthreads();
-        }
-        for (uint32_t tb = 0; tb < un; tb += tl) {   // the exchanges narrower than a tile
-          const uint32_t len = un - tb < tl ? un - tb : tl;
-          for (uint32_t p = tid; p < len; p += NT) s_key[p] = gk[tb + p];
-          __syncthreads();
-          for (uint32_t j = tl >> 1; j > 0; j >>= 1) {
-            bit_step<NT>(s_key, len, j);
-            __syncthreads();
-          }
-          for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s_key[p];
-          __syncthreads();
-        }
-      }
+      seg_sort<NT>(gk, s_key, un, (uint32_t)tile);
     }
     // edges: NumPy's lerp on the sorted keys, as deciles.inc
     const double* srt = SMALL ? s_key : gk;
@@ -438,6 +459,269 @@ __global__ __launch_bounds__(GS_THREADS) void k_gstats(
   }
 }
 
+// -------------------------------------------------------------------------------- I1, I2
+// the number of srt[0..n) (ascending) below x (LE: not above x), known to lie in [lo, hi]
+template <bool LE>
+__device__ __forceinline__ int count_to(const double* srt, int lo, int hi, double x) {
+  while (lo < hi) {
+    const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+    const double v = srt[mid];
+    if (LE ? v <= x : v < x)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+// Past the LDS cap the sorted keys are in the packed row; every stride-th of them is staged in
+// LDS (s[j] = srt[j * stride], at most cap samples), so a search makes its first steps in LDS and
+// the last log2(stride) in the row.
+struct Samples {
+  int m, stride;
+};
+template <int NT>
+__device__ __forceinline__ Samples stage_samples(const double* srt, int n, double* s, int cap) {
+  Samples sp;
+  sp.stride = (n + cap - 1) / cap;
+  sp.m = (n + sp.stride - 1) / sp.stride;
+  for (int j = threadIdx.x; j < sp.m; j += NT) s[j] = srt[(int64_t)j * sp.stride];
+  return sp;
+}
+template <bool LE>
+__device__ __forceinline__ int count_to(const double* srt, int n, const double* s, Samples sp,
+                                        double x) {
+  const int c = count_to<LE>(s, 0, sp.m, x);   // sample c - 1 counts, sample c does not
+  return count_to<LE>(srt, c > 0 ? (c - 1) * sp.stride + 1 : 0, c < sp.m ? c * sp.stride : n, x);
+}
+
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_rank(
+    const double* __restrict__ S, int64_t N, int n_groups, int method, int pct, int cap, int tile,
+    const int32_t* __restrict__ SEG, const uint32_t* __restrict__ SI, double* SK,
+    double* __restrict__ RANK) {
+  constexpr int NT = SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS;
+  __shared__ double s_key[GD_TILE];
+  const int64_t cell = blockIdx.x;
+  const int t = (int)(cell / n_groups), g = (int)(cell % n_groups);
+  const int tid = threadIdx.x;
+  const int seg0 = SEG[(int64_t)t * (n_groups + 1) + g];
+  const int n = SEG[(int64_t)t * (n_groups + 1) + g + 1] - seg0;
+  if (SMALL ? n > cap : n <= cap) return;   // the other launch's segment (block-uniform)
+  double* gk = SK + (int64_t)t * N + seg0;
+  const uint32_t* __restrict__ si = SI + (int64_t)t * N + seg0;
+  if (SMALL) {
+    for (int p = tid; p < n; p += NT) s_key[p] = gk[p];
+    __syncthreads();
+    tile_sort<NT>(s_key, (uint32_t)n);
+  } else {
+    seg_sort<NT>(gk, s_key, (uint32_t)n, (uint32_t)tile);
+  }
+  Samples sp{};
+  if (!SMALL) {
+    sp = stage_samples<NT>(gk, n, s_key, GD_TILE);
+    __syncthreads();
+  }
+  for (int p = tid; p < n; p += NT) {
+    const int64_t idx = (int64_t)t * N + si[p];
+    const double x = SMALL ? gk[p] : S[idx];   // (the LDS kernel leaves the packed keys unsorted)
+    const int lt = SMALL ? count_to<false>(s_key, 0, n, x) : count_to<false>(gk, n, s_key, sp, x);
+    const int le = SMALL ? count_to<true>(s_key, 0, n, x) : count_to<true>(gk, n, s_key, sp, x);
+    double r = method == 0 ? (double)(lt + le + 1) / 2.0 : (double)(method == 1 ? lt + 1 : le);
+    if (pct) r = r / (double)n;
+    RANK[idx] = r;
+  }
+}
+
+// -------------------------------------------------------------------------------- I3..I6
+#define IC_THREADS 1024
+__device__ __forceinline__ long long gwave_tree(long long v) {
+#pragma unroll
+  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
+  return v;
+}
+
+// I3.  One workgroup per month; each wave owns one contiguous chunk of the row.  The assets with
+// S[t] and Y[t + lead] both not NaN go, in asset order, to IX (their indices) and KS / KY (their
+// values); CN[t] is their number.
+__global__ __launch_bounds__(IC_THREADS) void k_icpart(
+    const double* __restrict__ S, const double* __restrict__ Y, int T_m, int64_t N, int lead,
+    uint32_t* __restrict__ IX, double* __restrict__ KS, double* __restrict__ KY,
+    int32_t* __restrict__ CN, int32_t* __restrict__ NOBS) {
+  __shared__ int s_cnt[IC_THREADS / 64];
+  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if ((int64_t)t + lead >= T_m) {   // (block-uniform)
+    if (tid == 0) {
+      CN[t] = 0;
+      if (NOBS) NOBS[t] = 0;
+    }
+    return;
+  }
+  const double* __restrict__ rs = S + (int64_t)t * N;
+  const double* __restrict__ ry = Y + ((int64_t)t + lead) * N;
+  const int64_t per = ((N + IC_THREADS - 1) / IC_THREADS) * 64;   // cells of one wave's chunk
+  const int64_t i0 = (int64_t)wave * per;
+  const int64_t i1 = i0 + per < N ? i0 + per : N;
+  int c = 0;
+  for (int64_t b = i0; b < i1; b += 64) {   // (wave-uniform trips)
+    const int64_t i = b + lane;
+    bool ok = false;
+    if (i < i1) {
+      const double s = rs[i], y = ry[i];
+      ok = s == s && y == y;
+    }
+    c += __popcll(__ballot(ok));
+  }
+  if (lane == 0) s_cnt[wave] = c;
+  __syncthreads();
+  int base = 0, tot = 0;
+  for (int w = 0; w < IC_THREADS / 64; ++w) {
+    const int v = s_cnt[w];
+    base += w < wave ? v : 0;
+    tot += v;
+  }
+  if (tid == 0) {
+    CN[t] = tot;
+    if (NOBS) NOBS[t] = tot;
+  }
+  uint32_t* __restrict__ ix = IX + (int64_t)t * N;
+  double* __restrict__ ks = KS + (int64_t)t * N;
+  double* __restrict__ ky = KY + (int64_t)t * N;
+  for (int64_t b = i0; b < i1; b += 64) {
+    const int64_t i = b + lane;
+    double s = qnan(), y = qnan();
+    if (i < i1) {
+      s = rs[i];
+      y = ry[i];
+    }
+    const bool ok = s == s && y == y;
+    const uint64_t m = __ballot(ok);
+    if (ok) {
+      const int pos = base + lane_prefix(m);
+      ix[pos] = (uint32_t)i;
+      ks[pos] = s;
+      ky[pos] = y;
+    }
+    base += __popcll(m);
+  }
+}
+
+// I5, on the packed values in asset order (before k_ic sorts them)
+__global__ __launch_bounds__(GS_THREADS) void k_icpearson(
+    int64_t N, int min_obs, const int32_t* __restrict__ CN, const double* __restrict__ KS,
+    const double* __restrict__ KY, double* __restrict__ PIC) {
+  __shared__ double s_part[GS_THREADS / 64];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int n = CN[t];
+  if (n < min_obs) {   // (block-uniform)
+    if (tid == 0) PIC[t] = qnan();
+    return;
+  }
+  const double* __restrict__ ks = KS + (int64_t)t * N;
+  const double* __restrict__ ky = KY + (int64_t)t * N;
+  double a = 0.0, b = 0.0;
+  for (int p = tid; p < n; p += GS_THREADS) {
+    a = a + ks[p];
+    b = b + ky[p];
+  }
+  const double ms = gs_block_sum(a, s_part) / (double)n;
+  const double my = gs_block_sum(b, s_part) / (double)n;
+  double qss = 0.0, qyy = 0.0, qsy = 0.0;
+  for (int p = tid; p < n; p += GS_THREADS) {
+    const double ds = ks[p] - ms, dy = ky[p] - my;
+    qss = qss + ds * ds;
+    qyy = qyy + dy * dy;
+    qsy = qsy + ds * dy;
+  }
+  const double css = gs_block_sum(qss, s_part);
+  const double cyy = gs_block_sum(qyy, s_part);
+  const double csy = gs_block_sum(qsy, s_part);
+  if (tid == 0) PIC[t] = (css > 0.0 && cyy > 0.0) ? csy / sqrt(css * cyy) : qnan();
+}
+
+// I4.  One workgroup per month.  SMALL: at most `cap` observations -- S's keys sorted in LDS, each
+// position's centred doubled rank a kept as int32, then Y's keys sorted in the same buffer.
+// Otherwise both packed rows are sorted in place (seg_sort) and each position's values are re-read
+// from S and Y through IX.  The three sums are integers: exact in any order.
+template <bool SMALL>
+__global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_ic(
+    const double* __restrict__ S, const double* __restrict__ Y, int64_t N, int lead, int min_obs,
+    int cap, int tile, const int32_t* __restrict__ CN, const uint32_t* __restrict__ IX, double* KS,
+    double* KY, double* __restrict__ RIC) {
+  constexpr int NT = SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS;
+  __shared__ double s_key[GD_TILE];
+  __shared__ int32_t s_a[SMALL ? GD_TILE : 1];
+  __shared__ long long s_red[NT / 64][3];
+  const int t = blockIdx.x, tid = threadIdx.x;
+  const int n = CN[t];
+  if (SMALL ? n > cap : n <= cap) return;   // the other launch's month (block-uniform)
+  if (n < min_obs) {
+    if (tid == 0) RIC[t] = qnan();
+    return;
+  }
+  double* ks = KS + (int64_t)t * N;
+  double* ky = KY + (int64_t)t * N;
+  long long sab = 0, saa = 0, sbb = 0;
+  if (SMALL) {
+    for (int p = tid; p < n; p += NT) s_key[p] = ks[p];
+    __syncthreads();
+    tile_sort<NT>(s_key, (uint32_t)n);
+    for (int p = tid; p < n; p += NT) {
+      const double x = ks[p];
+      s_a[p] = count_to<false>(s_key, 0, n, x) + count_to<true>(s_key, 0, n, x) - n;
+    }
+    __syncthreads();
+    for (int p = tid; p < n; p += NT) s_key[p] = ky[p];
+    __syncthreads();
+    tile_sort<NT>(s_key, (uint32_t)n);
+    for (int p = tid; p < n; p += NT) {
+      const double y = ky[p];
+      const long long a = s_a[p];
+      const long long b = count_to<false>(s_key, 0, n, y) + count_to<true>(s_key, 0, n, y) - n;
+      sab += a * b;
+      saa += a * a;
+      sbb += b * b;
+    }
+  } else {
+    seg_sort<NT>(ks, s_key, (uint32_t)n, (uint32_t)tile);
+    seg_sort<NT>(ky, s_key, (uint32_t)n, (uint32_t)tile);
+    double* s_ys = s_key + GD_TILE / 2;   // half of the buffer for each row's samples
+    const Samples ps = stage_samples<NT>(ks, n, s_key, GD_TILE / 2);
+    const Samples py = stage_samples<NT>(ky, n, s_ys, GD_TILE / 2);
+    __syncthreads();
+    const uint32_t* __restrict__ ix = IX + (int64_t)t * N;
+    const double* __restrict__ rs = S + (int64_t)t * N;
+    const double* __restrict__ ry = Y + ((int64_t)t + lead) * N;
+    for (int p = tid; p < n; p += NT) {
+      const double x = rs[ix[p]], y = ry[ix[p]];
+      const long long a =
+          count_to<false>(ks, n, s_key, ps, x) + count_to<true>(ks, n, s_key, ps, x) - n;
+      const long long b =
+          count_to<false>(ky, n, s_ys, py, y) + count_to<true>(ky, n, s_ys, py, y) - n;
+      sab += a * b;
+      saa += a * a;
+      sbb += b * b;
+    }
+  }
+  sab = gwave_tree(sab);
+  saa = gwave_tree(saa);
+  sbb = gwave_tree(sbb);
+  if ((tid & 63) == 0) {
+    s_red[tid >> 6][0] = sab;
+    s_red[tid >> 6][1] = saa;
+    s_red[tid >> 6][2] = sbb;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    long long ab = 0, aa = 0, bb = 0;
+    for (int w = 0; w < NT / 64; ++w) {
+      ab += s_red[w][0];
+      aa += s_red[w][1];
+      bb += s_red[w][2];
+    }
+    RIC[t] = (aa > 0 && bb > 0) ? (double)ab / sqrt((double)aa * (double)bb) : qnan();
+  }
+}
+
 // ----------------------------------------------------------------------------------- host
 struct GrpWs {
   int32_t* seg;    // [T_m][n_groups + 1] segment offsets in the packed row
@@ -475,10 +759,11 @@ static int grp_reserve(csm_ctx* ctx, const char* who, int32_t T_m, int64_t N, in
   return CSM_OK;
 }
 
-// the checks the two entry points share
+// the checks the grouped entry points share (gid_opt: a NULL GID is the caller's to judge)
 static int grp_check(csm_ctx* ctx, const char* who, const double* S, const int16_t* GID,
-                     int64_t g_ld, int32_t T_m, int64_t N, int32_t n_groups) {
-  if (!S || !GID || T_m < 1 || N < 1 || N > 0x7FFFFFFFLL || (int64_t)T_m > ((int64_t)1 << 40) / N)
+                     int64_t g_ld, int32_t T_m, int64_t N, int32_t n_groups,
+                     bool gid_opt = false) {
+  if (!S || (!GID && !gid_opt) || T_m < 1 || N < 1 || N > 0x7FFFFFFFLL || (int64_t)T_m > ((int64_t)1 << 40) / N)
     return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld)", who, T_m, (long long)N);
   if (n_groups < 1 || n_groups > GP_MAXG)
     return set_err(ctx, CSM_E_INVAL, "%s: n_groups=%d is outside [1, %d]", who, n_groups, GP_MAXG);
@@ -561,6 +846,87 @@ int csm_group_stats(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g
   hipLaunchKernelGGL(k_gstats, dim3((unsigned)((int64_t)T_m * n_groups)), dim3(GS_THREADS), 0,
                      ctx->stream, N, n_groups, w.seg, w.si, w.sk, GMEAN, GSD, GCNT, SA, SZ, SB);
   LAUNCH_CHECK(ctx, "k_gstats");
+  return CSM_OK;
+}
+
+int csm_xs_rank(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g_ld, int32_t T_m,
+                int64_t N, int32_t n_groups, int32_t method, int32_t pct, double* RANK,
+                int32_t* NVG) {
+  const char* who = "csm_xs_rank";
+  int r = prep(ctx);
+  if (r) return r;
+  r = grp_check(ctx, who, S, GID, g_ld, T_m, N, n_groups, true);
+  if (r) return r;
+  if (!RANK) return set_err(ctx, CSM_E_INVAL, "%s: RANK is NULL", who);
+  if (!GID && n_groups != 1)
+    return set_err(ctx, CSM_E_INVAL, "%s: GID is NULL with n_groups=%d (one group only)", who,
+                   n_groups);
+  if (method < 0 || method > 2)
+    return set_err(ctx, CSM_E_INVAL, "%s: method=%d is not 0 (average), 1 (min) or 2 (max)", who,
+                   method);
+  GrpWs w;
+  r = grp_reserve(ctx, who, T_m, N, n_groups, 1, &w);
+  if (r) return r;
+  const int cap = g_tune_gdec_small_cap;
+  int tile = 2;
+  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  hipLaunchKernelGGL(k_gpart, dim3((unsigned)T_m), dim3(GP_THREADS), 0, ctx->stream, S, GID, g_ld,
+                     N, n_groups, w.seg, w.si, w.sk, (int8_t*)nullptr, NVG, (int32_t*)nullptr, RANK,
+                     (double*)nullptr, (double*)nullptr);
+  LAUNCH_CHECK(ctx, "k_gpart");
+  const unsigned segs = (unsigned)((int64_t)T_m * n_groups);
+  hipLaunchKernelGGL(k_rank<true>, dim3(segs), dim3(GD_SMALL_THREADS), 0, ctx->stream, S, N,
+                     n_groups, method, pct, cap, tile, w.seg, w.si, w.sk, RANK);
+  LAUNCH_CHECK(ctx, "k_rank (LDS)");
+  hipLaunchKernelGGL(k_rank<false>, dim3(segs), dim3(GD_LONG_THREADS), 0, ctx->stream, S, N,
+                     n_groups, method, pct, cap, tile, w.seg, w.si, w.sk, RANK);
+  LAUNCH_CHECK(ctx, "k_rank (tiled)");
+  return CSM_OK;
+}
+
+int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int64_t N,
+                int32_t lead, int32_t min_obs, double* RIC, double* PIC, int32_t* NOBS) {
+  const char* who = "csm_rank_ic";
+  int r = prep(ctx);
+  if (r) return r;
+  if (!S || !Y || T_m < 1 || N < 1 || lead < 0)
+    return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld lead=%d)", who, T_m,
+                   (long long)N, lead);
+  if (N > ((int64_t)1 << 20))   // |a| < n <= 2^20: the int64 sums of I4 stay below 2^60
+    return set_err(ctx, CSM_E_INVAL, "%s: N=%lld exceeds 2^20", who, (long long)N);
+  if (min_obs < 2)
+    return set_err(ctx, CSM_E_INVAL, "%s: min_obs=%d must be at least 2", who, min_obs);
+  if (!RIC && !PIC) return set_err(ctx, CSM_E_INVAL, "%s: RIC and PIC are both NULL", who);
+  // the index list and two key rows (20 B per cell), the months' counts
+  const size_t cells = (size_t)T_m * (size_t)N;
+  const size_t b_k = up16(cells * sizeof(double)), b_ix = up16(cells * sizeof(uint32_t));
+  r = ctx_reserve(ctx, who, "the group partition workspace", &ctx->grp_ws, &ctx->grp_ws_bytes,
+                  2 * b_k + b_ix + up16((size_t)T_m * sizeof(int32_t)));
+  if (r) return r;
+  char* p = (char*)ctx->grp_ws;
+  double* ks = (double*)p;
+  double* ky = (double*)(p + b_k);
+  uint32_t* ix = (uint32_t*)(p + 2 * b_k);
+  int32_t* cn = (int32_t*)(p + 2 * b_k + b_ix);
+  const int cap = g_tune_gdec_small_cap;
+  int tile = 2;
+  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  hipLaunchKernelGGL(k_icpart, dim3((unsigned)T_m), dim3(IC_THREADS), 0, ctx->stream, S, Y, T_m, N,
+                     lead, ix, ks, ky, cn, NOBS);
+  LAUNCH_CHECK(ctx, "k_icpart");
+  if (PIC) {
+    hipLaunchKernelGGL(k_icpearson, dim3((unsigned)T_m), dim3(GS_THREADS), 0, ctx->stream, N,
+                       min_obs, cn, ks, ky, PIC);
+    LAUNCH_CHECK(ctx, "k_icpearson");
+  }
+  if (RIC) {
+    hipLaunchKernelGGL(k_ic<true>, dim3((unsigned)T_m), dim3(GD_SMALL_THREADS), 0, ctx->stream, S,
+                       Y, N, lead, min_obs, cap, tile, cn, ix, ks, ky, RIC);
+    LAUNCH_CHECK(ctx, "k_ic (LDS)");
+    hipLaunchKernelGGL(k_ic<false>, dim3((unsigned)T_m), dim3(GD_LONG_THREADS), 0, ctx->stream, S,
+                       Y, N, lead, min_obs, cap, tile, cn, ix, ks, ky, RIC);
+    LAUNCH_CHECK(ctx, "k_ic (tiled)");
+  }
   return CSM_OK;
 }
 

@@ -164,6 +164,28 @@ class GroupStatsOut:
 
 
 @dataclass
+class RankICOut:
+    """csm_rank_ic (rules I3..I6), each [T_m]."""
+    RIC: torch.Tensor                    # Spearman rank IC of S[t] with Y[t + lead] (NaN = undefined)
+    PIC: torch.Tensor | None             # Pearson IC on the same observations; None = not asked for
+    NOBS: torch.Tensor                   # int32, the month's observations
+
+
+@dataclass
+class ICDecayOut:
+    """Engine.ic_decay: rank_ic per horizon and the Newey-West summary of each horizon's series."""
+    RIC: torch.Tensor                    # [H][T_m]
+    PIC: torch.Tensor                    # [H][T_m]
+    NOBS: torch.Tensor                   # [H][T_m] int32
+    MEAN: torch.Tensor                   # [H] time-series mean of RIC's rows
+    SE: torch.Tensor                     # [H] its Newey-West standard error
+    T: torch.Tensor                      # [H]
+    NT: torch.Tensor                     # [H] int32, the months behind each
+    horizons: tuple = ()
+    lags: int = 0
+
+
+@dataclass
 class ShardState:
     """signal_shard's end-state record [5][N] (present months, pending ranked row, its
     subset-ffilled price, first / last present month) with the daily panel it came from
@@ -985,6 +1007,59 @@ class Engine:
         r2 = self.newey_west(r.R2, lags)
         return FamaMacBethOut(GAMMA=r.GAMMA, R2=r.R2, NOBS=r.NOBS, MEAN=nw.MEAN, SE=nw.SE, T=nw.T,
                               NT=nw.NT, R2_MEAN=r2.MEAN, lags=lags)
+
+    # ------------------------------------------------------------------ ranks and ICs
+    RANK_METHODS = {"average": 0, "min": 1, "max": 2}
+
+    def xs_rank(self, S, GID=None, n_groups=1, method="average", pct=False, out=None,
+                with_nvg=False):
+        """csm_xs_rank (rules I1, I2): the rank of S [T_m][N] inside each date, or with GID (int16
+        [T_m][N] or a static [N]) inside each (date, group) -- pandas' rank(method='average' |
+        'min' | 'max', pct=pct); NaN outside every group.  with_nvg: returns (RANK, NVG) with the
+        member counts [T_m][n_groups]."""
+        T_m, N = S.shape
+        _need(S, "S", torch.float64, (T_m, N), self.device)
+        if method not in self.RANK_METHODS:
+            raise ValueError(f"method must be one of {tuple(self.RANK_METHODS)}, got {method!r}")
+        g_ld = 0
+        if GID is not None:
+            GID, g_ld = self._group_ids(GID, T_m, N)
+        G = int(n_groups)
+        RANK = self.empty((T_m, N)) if out is None else out
+        _need(RANK, "out", torch.float64, (T_m, N), self.device)
+        NVG = self.empty((T_m, max(G, 1)), torch.int32) if with_nvg else None
+        self._call("csm_xs_rank", _ptr(S), _ptr(GID), g_ld, T_m, N, G, self.RANK_METHODS[method],
+                   int(bool(pct)), _ptr(RANK), _ptr(NVG))
+        return (RANK, NVG) if with_nvg else RANK
+
+    def rank_ic(self, S, Y, lead=0, min_obs=10, pearson=True) -> RankICOut:
+        """csm_rank_ic (rules I3..I6): per month t the Spearman rank correlation RIC, and with
+        pearson the Pearson correlation PIC, of S[t] with Y[t + lead] across the assets where
+        both are not NaN; NaN with fewer than min_obs of them or no variation."""
+        T_m, N = S.shape
+        _need(S, "S", torch.float64, (T_m, N), self.device)
+        _need(Y, "Y", torch.float64, (T_m, N), self.device)
+        RIC = self.empty((T_m,))
+        PIC = self.empty((T_m,)) if pearson else None
+        NOBS = self.empty((T_m,), torch.int32)
+        self._call("csm_rank_ic", _ptr(S), _ptr(Y), T_m, N, int(lead), int(min_obs), _ptr(RIC),
+                   _ptr(PIC), _ptr(NOBS))
+        return RankICOut(RIC=RIC, PIC=PIC, NOBS=NOBS)
+
+    def ic_decay(self, S, X, horizons=(1, 2, 3, 6, 12), min_obs=10, lags=None) -> ICDecayOut:
+        """The IC of S at each horizon h: rank_ic(S, X, lead=h), stacked [H][T_m], and one
+        newey_west over the H series.  With X the month return (rule B1) horizon h is the return
+        of the h-th month after formation."""
+        hs = tuple(int(h) for h in horizons)
+        if not hs:
+            raise ValueError("horizons is empty")
+        r = [self.rank_ic(S, X, lead=h, min_obs=min_obs) for h in hs]
+        RIC = torch.stack([o.RIC for o in r])
+        lags = self.default_lags(S.shape[0]) if lags is None else int(lags)
+        nw = self.newey_west(RIC.t().contiguous(), lags)
+        return ICDecayOut(RIC=RIC, PIC=torch.stack([o.PIC for o in r]),
+                          NOBS=torch.stack([o.NOBS for o in r]), MEAN=nw.MEAN, SE=nw.SE, T=nw.T,
+                          NT=nw.NT, horizons=hs, lags=lags)
 
     # ------------------------------------------------------------------ within-group sorts
     def _group_ids(self, GID, T_m, N):

@@ -61,18 +61,24 @@ def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None)
 
 
 def fama_macbeth(daily_df, signals=("mom", "high52", "beta", "ivol"), J=12, skip=1, window=None,
-                 weights=None, standardize=True, ridge=0.0, lags=None, device=None):
+                 weights=None, standardize=True, ridge=0.0, lags=None, device=None,
+                 transform=None):
     """Fama-MacBeth regressions of next month's return on the named signals.  Y[t] is the month
     return (rule B1) of month t + 1; weights, when given, is a [T_m][N] array or tensor in the
-    dense panel's layout (from_long).  Returns a FamaMacBethResult, or None when the frame holds
-    no month."""
+    dense panel's layout (from_long).  transform "rank" replaces each signal by its
+    cross-sectional percentile rank (Engine.xs_rank(pct=True), rules I1, I2) before the
+    regressions.  Returns a FamaMacBethResult, or None when the frame holds no month."""
     names = tuple(signals)
+    if transform not in (None, "rank"):
+        raise ValueError(f"transform must be None or 'rank', got {transform!r}")
     panel = from_long(daily_df)
     if panel.P.size == 0 or panel.T_m == 0:
         return None
     eng = get_engine(device)
     P, _, ms = upload_panel(panel, eng, with_volume=False)
     S, X = build_signals(eng, P, ms, names, J, skip, window)
+    if transform == "rank":
+        S = [eng.xs_rank(s, pct=True) for s in S]
     Y = torch.cat([X[1:], torch.full_like(X[:1], float("nan"))])
     W = None
     if weights is not None:

@@ -805,6 +805,52 @@ int csm_group_stats(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g
                     double* SA, double* SZ, double* SB);
 
 /*
+ * Cross-sectional ranks and information coefficients (rules I1..I6 in DESIGN.md section 7):
+ * pandas' rank(axis=1, method='average' | 'min' | 'max', pct=...) per date or per (date, group),
+ * and the per-month Spearman and Pearson correlation of a signal with a later return (scipy's
+ * spearmanr, pandas' corr(method='spearman')).  Ranks are integers or half-integers and the
+ * Spearman sums are integers, so both are functions of the data alone: no tolerance.
+ * method='first' and 'dense' are not offered: a stable order needs a (key, index) pair sort and
+ * dense ranks a distinct-count scan, neither is needed for the IC, and the reference's 'first'
+ * fallback (run_demo.py:25-29) is unreachable for finite input.
+ *
+ * csm_xs_rank:  S [T_m][N]; GID, g_ld, n_groups as csm_group_deciles.
+ *   I1  membership is rule N1.  GID == NULL is allowed with n_groups == 1 only: every non-NaN
+ *       cell is a member of group 0.  Non-members get NaN in RANK [T_m][N]; NVG [T_m][n_groups]
+ *       int32 (nullable) receives the member counts.
+ *   I2  a member with value x in a segment of n members: lt = the members with value < x, le =
+ *       those with value <= x (-0.0 and 0.0 tie).  method 0 (average) = (lt + le + 1) / 2.0,
+ *       1 (min) = lt + 1, 2 (max) = le; with pct != 0 that rank divided by (double)n, one fp64
+ *       division (pandas' rank(pct=True)).
+ *   CSM_E_INVAL as csm_group_stats, plus: a method outside 0..2, a NULL S or RANK, GID == NULL with
+ *   n_groups != 1.  "gdec_small_cap" moves the LDS / tiled hand-over here too; the output does not
+ *   depend on it.
+ *
+ * csm_rank_ic:  S, Y [T_m][N].
+ *   I3  month t pairs S[t][a] with Y[t + lead][a], lead >= 0; asset a is an observation iff both
+ *       are not NaN; n = NOBS[t] their number.  Months with t + lead >= T_m have NOBS = 0 and NaN
+ *       outputs.  Ranks are taken inside the joint observation set, not over S alone.
+ *   I4  with lt, le as in I2 over the observations, a = lt_s + le_s - n (= 2 rank - (n + 1), an
+ *       integer) and b likewise from Y; Sab = sum a * b, Saa = sum a * a, Sbb = sum b * b in
+ *       int64 (|a| < n <= 2^20: exact in any order).  RIC = (double)Sab / sqrt((double)Saa *
+ *       (double)Sbb), each conversion rounding once; defined iff n >= min_obs, Saa > 0, Sbb > 0.
+ *   I5  the observations stand in asset order at positions 0..n-1; every sum in N4's order (lane l
+ *       of 256 adds positions l, l + 256, ... from 0.0, each wave by the halving tree, the four
+ *       wave sums in order from 0.0).  ms = (sum s) / n, my = (sum y) / n; ds = s - ms, dy = y - my;
+ *       css = sum ds * ds, cyy = sum dy * dy, csy = sum ds * dy; PIC = csy / sqrt(css * cyy),
+ *       defined iff n >= min_obs, css > 0, cyy > 0.  A function of n alone: no atomic.
+ *   I6  RIC, PIC [T_m] out, NOBS [T_m] int32 out, each nullable, RIC or PIC required; NOBS is
+ *       written for every month.  Scratch (20 B per cell) is the context's.
+ *   CSM_E_INVAL: a NULL S or Y, RIC and PIC both NULL, T_m < 1, N < 1, N > 2^20, lead < 0,
+ *   min_obs < 2.  +-inf in the data is out of contract.
+ */
+int csm_xs_rank(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g_ld, int32_t T_m,
+                int64_t N, int32_t n_groups, int32_t method, int32_t pct, double* RANK,
+                int32_t* NVG);
+int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int64_t N,
+                int32_t lead, int32_t min_obs, double* RIC, double* PIC, int32_t* NOBS);
+
+/*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
  * month-return panel R[T_m][N] (csm_momentum's R; NaN = no row).  src[B][T_m] int32 out: the
  * source months; PMb[T_m][B][N] out: month prices p0 * prod(1 + r) over the resampled months,
