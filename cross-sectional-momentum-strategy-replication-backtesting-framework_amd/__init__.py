@@ -26,6 +26,9 @@ a Python identifier).  Public API (reference file:line it replaces):
   dependent_double_sort                 n1 bins of one signal, n2 bins of another inside each
   Engine.xs_rank / rank_ic / ic_decay   cross-sectional ranks, per-month Spearman and Pearson ICs
   information_coefficient               and their decay over horizons (rules I1..I6)
+  Engine.deciles_bp / breakpoints       qcut edges from a subset of each date (NYSE breakpoints) applied
+  Engine.screen / run_universe          to every cell, the edges themselves, price and size screens
+  universe_momentum                     (rules U1..U6)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
@@ -39,6 +42,7 @@ from .features import compute_monthly_momentum_from_daily, compute_monthly_turno
 from .lesw import (DependentSortResult, DoubleSortResult, dependent_double_sort,
                    momentum_volume_double_sort)
 from .neutral import NeutralResult, group_ids, neutral_momentum
+from .universe import UniverseResult, breakpoint_mask, shares_row, universe_momentum
 from .regress import FamaMacBethResult, fama_macbeth
 from .ic import ICResult, information_coefficient
 from .panel import DensePanel, from_long, month_offsets, monthly_frame
@@ -60,4 +64,5 @@ __all__ = [
     "fama_macbeth", "GroupStatsOut", "DependentSortResult", "dependent_double_sort",
     "NeutralResult", "group_ids", "neutral_momentum",
     "RankICOut", "ICDecayOut", "ICResult", "information_coefficient",
+    "UniverseResult", "breakpoint_mask", "shares_row", "universe_momentum",
 ]

@@ -108,6 +108,9 @@ SIGNATURES = {
                                        _p]),
     "csm_xs_rank": (ctypes.c_int, [_p, _p, _p, _i64, _i32, _i64, _i32, _i32, _i32, _p, _p]),
     "csm_rank_ic": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, _i32, _p, _p, _p]),
+    "csm_deciles_bp": (ctypes.c_int, [_p, _p, _p, _p, _i64, _i32, _i64, _i32, _p, _p, _p, _p, _p, _p,
+                                      _p, _p]),
+    "csm_screen": (ctypes.c_int, [_p, _p, _p, _f64, _p, _p, _i32, _i64, _p, _p]),
     "csm_bootstrap": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64,
                                      _f64, _p, _p]),
     "csm_boot_scan": (ctypes.c_int, [_p, _p, _i32, _i64, _i32, _i64, ctypes.c_uint64, _f64, _f64,

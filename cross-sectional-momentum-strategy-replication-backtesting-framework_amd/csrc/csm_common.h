@@ -52,7 +52,8 @@ struct csm_ctx {
   size_t xs_ws_bytes;     // long for csm_newey_west's LDS (xsreg.hip), grown lazily
   void* grp_ws;           // csm_group_deciles / csm_group_stats: the packed rows, segment offsets
   size_t grp_ws_bytes;    // and per-group sums; csm_xs_rank's the same, csm_rank_ic's index list
-                          // and key rows (groups.hip), grown lazily
+                          // and key rows (groups.hip), csm_deciles_bp's packed keys and edges
+                          // (breakpoints.hip), grown lazily
 };
 
 static inline int set_err(csm_ctx* c, int code, const char* fmt, ...) {

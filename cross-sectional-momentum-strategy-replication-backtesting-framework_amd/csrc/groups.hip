@@ -43,15 +43,12 @@
 //              list.  The three sums are int64: exact in any order.
 //
 // No floating-point atomic anywhere: two calls give the same bits.
-#include "csm_common.h"
+#include "gsort.h"   // the wave tree, tile_sort / seg_sort, qcut_edge
 
 #define GP_THREADS 1024
 #define GP_WAVES (GP_THREADS / 64)
 #define GP_MAXG 256        // n_groups <= 256
 #define GP_U 4             // steps of 64 cells whose loads a wave issues together
-#define GD_TILE 4096       // keys of one LDS sort (32 KiB)
-#define GD_SMALL_THREADS 256
-#define GD_LONG_THREADS 1024
 #define GS_THREADS 256
 
 // segments of at most this many keys take the LDS kernel (csm_tune "gdec_small_cap" lowers it;
@@ -61,17 +58,6 @@ static int g_tune_gdec_small_cap = GD_TILE;
 static const TuneKnob g_knobs[] = {
     {"gdec_small_cap", &g_tune_gdec_small_cap, [](int v) { return v >= 1 && v <= GD_TILE; }},
 };
-
-__device__ __forceinline__ double gwave_tree(double v) {
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
-  return v;
-}
-__device__ __forceinline__ int gwave_tree(int v) {
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
-  return v;
-}
 
 // ------------------------------------------------------------------------------------ N1
 // the group of cell i of the row, -1 for none
@@ -204,81 +190,6 @@ __global__ __launch_bounds__(GP_THREADS) void k_gpart(
 }
 
 // ------------------------------------------------------------------------------------ N2
-__device__ __forceinline__ void cmpx(double* a, uint32_t lo, uint32_t hi) {
-  const double x = a[lo], y = a[hi];
-  if (x > y) {
-    a[lo] = y;
-    a[hi] = x;
-  }
-}
-// the first exchange of the merge of width k: lo with lo ^ (k - 1), over a[0..len)
-template <int NT>
-__device__ __forceinline__ void bit_flip(double* a, uint32_t len, uint32_t k) {
-  const uint32_t h = k >> 1;
-  for (uint32_t q = threadIdx.x;; q += NT) {
-    const uint32_t lo = ((q & ~(h - 1)) << 1) | (q & (h - 1));
-    if (lo >= len) break;
-    const uint32_t hi = lo ^ (k - 1);
-    if (hi < len) cmpx(a, lo, hi);
-  }
-}
-// a later exchange of a merge: lo with lo + j
-template <int NT>
-__device__ __forceinline__ void bit_step(double* a, uint32_t len, uint32_t j) {
-  for (uint32_t q = threadIdx.x;; q += NT) {
-    const uint32_t lo = ((q & ~(j - 1)) << 1) | (q & (j - 1));
-    if (lo >= len) break;
-    const uint32_t hi = lo + j;
-    if (hi < len) cmpx(a, lo, hi);
-  }
-}
-// sorts s[0..len) (LDS), len <= GD_TILE
-template <int NT>
-__device__ __forceinline__ void tile_sort(double* s, uint32_t len) {
-  for (uint32_t k = 2; (k >> 1) < len; k <<= 1) {
-    bit_flip<NT>(s, len, k);
-    __syncthreads();
-    for (uint32_t j = k >> 2; j > 0; j >>= 1) {
-      bit_step<NT>(s, len, j);
-      __syncthreads();
-    }
-  }
-}
-
-// sorts gk[0..un) (the packed row), un past the LDS cap: tiles of tl keys sorted in s (LDS), the
-// exchanges wider than a tile made in gk itself
-template <int NT>
-__device__ __forceinline__ void seg_sort(double* gk, double* s, uint32_t un, uint32_t tl) {
-  const uint32_t tid = threadIdx.x;
-  for (uint32_t tb = 0; tb < un; tb += tl) {
-    const uint32_t len = un - tb < tl ? un - tb : tl;
-    for (uint32_t p = tid; p < len; p += NT) s[p] = gk[tb + p];
-    __syncthreads();
-    tile_sort<NT>(s, len);
-    for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s[p];
-    __syncthreads();
-  }
-  for (uint32_t k = 2 * tl; k != 0 && (k >> 1) < un; k <<= 1) {
-    bit_flip<NT>(gk, un, k);
-    __syncthreads();
-    for (uint32_t j = k >> 2; j >= tl; j >>= 1) {
-      bit_step<NT>(gk, un, j);
-      __syncthreads();
-    }
-    for (uint32_t tb = 0; tb < un; tb += tl) {   // the exchanges narrower than a tile
-      const uint32_t len = un - tb < tl ? un - tb : tl;
-      for (uint32_t p = tid; p < len; p += NT) s[p] = gk[tb + p];
-      __syncthreads();
-      for (uint32_t j = tl >> 1; j > 0; j >>= 1) {
-        bit_step<NT>(s, len, j);
-        __syncthreads();
-      }
-      for (uint32_t p = tid; p < len; p += NT) gk[tb + p] = s[p];
-      __syncthreads();
-    }
-  }
-}
-
 template <bool SMALL>
 __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_gdec(
     const double* __restrict__ S, const double* __restrict__ NR, int64_t N, int n_groups,
@@ -310,22 +221,7 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
     }
     // edges: NumPy's lerp on the sorted keys, as deciles.inc
     const double* srt = SMALL ? s_key : gk;
-    if (tid <= n_bins) {
-      const double v = (double)(n - 1) * qt.q[tid];
-      double ek;
-      if (v >= (double)(n - 1)) {
-        ek = srt[n - 1];
-      } else {
-        const double p = floor(v);
-        const double gm = v - p;
-        const int pi = (int)p;
-        const double a = srt[pi];
-        const double b = (gm != 0.0) ? srt[pi + 1] : a;
-        const double d = b - a;
-        ek = (gm >= 0.5) ? (b - d * (1.0 - gm)) : (a + d * gm);
-      }
-      s_edge[tid] = ek;
-    }
+    if (tid <= n_bins) s_edge[tid] = qcut_edge(srt, n, qt.q[tid]);
     __syncthreads();
     if (tid == 0) {   // duplicates='drop'
       int nu = 0;
@@ -731,8 +627,6 @@ struct GrpWs {
   double* sumg;    // [T_m][n_groups][n_bins]
   int32_t* cntg;   // [T_m][n_groups][n_bins]
 };
-
-static inline size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
 
 static int grp_reserve(csm_ctx* ctx, const char* who, int32_t T_m, int64_t N, int32_t n_groups,
                        int32_t n_bins, GrpWs* w) {

@@ -73,6 +73,12 @@ class PipelineOut:
     R: torch.Tensor | None = None
     VOL: torch.Tensor | None = None
     NV: torch.Tensor | None = None
+    # run_universe only: the breakpoint set's size, the screen's kept cells (None without a
+    # screen), the distinct edges and their number per date (rules U2, U5)
+    NVB: torch.Tensor | None = None
+    KEPT: torch.Tensor | None = None
+    EDGES: torch.Tensor | None = None
+    NE: torch.Tensor | None = None
 
 
 @dataclass
@@ -1153,6 +1159,134 @@ class Engine:
             L, EW, CNT, NV = self.deciles(S, NR, n_bins, with_nv=True)
         LS = self.long_short(EW, CNT)
         return PipelineOut(PM=PM, M=S, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, NV=NV)
+
+    # ------------------------------------------- reference-universe breakpoints and screens
+    def _bp_mask(self, BP, T_m, N):
+        """BP as csm_deciles_bp takes it: uint8 (or bool, reinterpreted) [T_m][N] (one row per
+        month) or [N] (static); returns (BP, bp_ld)."""
+        if not isinstance(BP, torch.Tensor) or BP.dtype not in (torch.uint8, torch.bool):
+            raise TypeError("BP must be a uint8 or bool torch tensor")
+        if BP.dim() == 1:
+            _need(BP, "BP", BP.dtype, (N,), self.device)
+            ld = 0
+        else:
+            _need(BP, "BP", BP.dtype, (T_m, N), self.device)
+            ld = N
+        return (BP.view(torch.uint8) if BP.dtype == torch.bool else BP), ld
+
+    def deciles_bp(self, M, NR, BP, n_bins=10, with_nv=False, with_edges=False):
+        """csm_deciles_bp (rules U1..U4): the qcut edges of each date from the cells with a
+        non-zero BP byte (NYSE breakpoints), every non-NaN cell of M labelled against them (below
+        the first edge: bin 0, above the last: the top bin), and with NR the decile means.  BP:
+        uint8 or bool [T_m][N] or a static [N].
+        Returns (L, EW, CNT[, NV, NVB][, EDGES, NE]); EW / CNT are None without NR."""
+        T_m, N = M.shape
+        _need(M, "M", torch.float64, (T_m, N), self.device)
+        if NR is not None:
+            _need(NR, "NR", torch.float64, (T_m, N), self.device)
+        BP, ld = self._bp_mask(BP, T_m, N)
+        nb = int(n_bins)
+        L = self.empty((T_m, N), torch.int8)
+        EW = self.empty((T_m, nb)) if NR is not None else None
+        CNT = self.empty((T_m, nb), torch.int32) if NR is not None else None
+        NV = self.empty((T_m,), torch.int32) if with_nv else None
+        NVB = self.empty((T_m,), torch.int32) if with_nv else None
+        EDGES = self.empty((T_m, max(nb, 0) + 1)) if with_edges else None
+        NE = self.empty((T_m,), torch.int32) if with_edges else None
+        q = quantile_table(nb) if nb >= 1 else np.zeros(1)
+        self._call("csm_deciles_bp", _ptr(M), _ptr(NR), _ptr(BP), ld, T_m, N, nb,
+                   q.ctypes.data_as(ctypes.c_void_p), _ptr(L), _ptr(EW), _ptr(CNT), _ptr(NV),
+                   _ptr(NVB), _ptr(EDGES), _ptr(NE))
+        out = (L, EW, CNT)
+        if with_nv:
+            out += (NV, NVB)
+        if with_edges:
+            out += (EDGES, NE)
+        return out
+
+    def breakpoints(self, S, BP, n_bins=10):
+        """The edges of csm_deciles_bp alone (rule U2, L = NULL): (EDGES [T_m][n_bins + 1], the
+        NE[t] distinct edges first and NaN after them, NE, NVB).  breakpoints(CAP, nyse, 10)[0][:, 1]
+        is the NYSE 10th-percentile size per month, the CAPMIN screen takes."""
+        T_m, N = S.shape
+        _need(S, "S", torch.float64, (T_m, N), self.device)
+        BP, ld = self._bp_mask(BP, T_m, N)
+        nb = int(n_bins)
+        EDGES = self.empty((T_m, max(nb, 0) + 1))
+        NE = self.empty((T_m,), torch.int32)
+        NVB = self.empty((T_m,), torch.int32)
+        q = quantile_table(nb) if nb >= 1 else np.zeros(1)
+        self._call("csm_deciles_bp", _ptr(S), None, _ptr(BP), ld, T_m, N, nb,
+                   q.ctypes.data_as(ctypes.c_void_p), None, None, None, None, _ptr(NVB),
+                   _ptr(EDGES), _ptr(NE))
+        return EDGES, NE, NVB
+
+    def screen(self, M, PM=None, min_price=None, CAP=None, CAPMIN=None, with_kept=False):
+        """csm_screen (rule U5): M where the cell passes the price screen (PM >= min_price) and
+        the size screen (CAP >= CAPMIN[t]), NaN elsewhere; a NaN PM, CAP or CAPMIN fails the cell.
+        A screen whose panel is None is not applied.  Returns MS, or (MS, KEPT) with with_kept."""
+        T_m, N = M.shape
+        _need(M, "M", torch.float64, (T_m, N), self.device)
+        if (PM is None) != (min_price is None):
+            raise ValueError("PM and min_price go together")
+        if (CAP is None) != (CAPMIN is None):
+            raise ValueError("CAP and CAPMIN go together")
+        if PM is not None:
+            _need(PM, "PM", torch.float64, (T_m, N), self.device)
+        if CAP is not None:
+            _need(CAP, "CAP", torch.float64, (T_m, N), self.device)
+            _need(CAPMIN, "CAPMIN", torch.float64, (T_m,), self.device)
+        MS = self.empty((T_m, N))
+        KEPT = self.empty((T_m,), torch.int32) if with_kept else None
+        self._call("csm_screen", _ptr(M), _ptr(PM), 0.0 if min_price is None else float(min_price),
+                   _ptr(CAP), _ptr(CAPMIN), T_m, N, _ptr(MS), _ptr(KEPT))
+        return (MS, KEPT) if with_kept else MS
+
+    def run_universe(self, P, month_start, BP=None, min_price=None, CAP=None, min_size_pct=None,
+                     signal="mom", J=12, skip=1, n_bins=10, window=12, min_obs=None) -> PipelineOut:
+        """One full pass on a screened universe with reference breakpoints (Jegadeesh-Titman
+        2001).  The signal is built as run_neutral builds it; cells whose formation-month price is
+        under min_price, or whose CAP [T_m][N] is under the min_size_pct percentile of the BP
+        subset's CAP that month, are screened out (rule U5); the rest are ranked by deciles_bp on
+        the BP subset's edges.  BP None: every cell is a breakpoint cell.  min_size_pct: a
+        percentage p with 100 / p one of 2, 3, 4, 5, 10, 20 (10: the smallest decile, 20: the
+        smallest quintile).  M is the screened signal and NR the signal's next return (rule U6)."""
+        if (CAP is None) != (min_size_pct is None):
+            raise ValueError("CAP and min_size_pct go together")
+        if signal == "mom":
+            PM, _ = self.month_end(P, month_start)
+            T_m, N = PM.shape
+            if self.default_chunks(T_m, N, J, skip) > 1:
+                _, S, NR = self.momentum_chunked(PM, J, skip)
+            else:
+                _, S, NR = self.momentum(PM, J, skip)
+        else:
+            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs)
+            PM, S, NR = r.PM, r.M, r.NR
+        T_m, N = S.shape
+        if BP is None:
+            BP = torch.ones((N,), dtype=torch.uint8, device=self.device)
+        CAPMIN = None
+        if CAP is not None:
+            nq = self.size_bins(min_size_pct)
+            CAPMIN = self.breakpoints(CAP, BP, nq)[0][:, 1].contiguous()
+        KEPT = None
+        if min_price is not None or CAP is not None:
+            S, KEPT = self.screen(S, PM if min_price is not None else None, min_price, CAP,
+                                  CAPMIN, with_kept=True)
+        L, EW, CNT, NV, NVB, EDGES, NE = self.deciles_bp(S, NR, BP, n_bins, with_nv=True,
+                                                         with_edges=True)
+        LS = self.long_short(EW, CNT)
+        return PipelineOut(PM=PM, M=S, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, NV=NV, NVB=NVB,
+                           KEPT=KEPT, EDGES=EDGES, NE=NE)
+
+    @staticmethod
+    def size_bins(min_size_pct):
+        """The n_bins whose edge 1 is the min_size_pct percentile: 100 / p, one of 2/3/4/5/10/20."""
+        for nq in (2, 3, 4, 5, 10, 20):
+            if abs(100.0 / nq - float(min_size_pct)) < 1e-9:
+                return nq
+        raise ValueError(f"min_size_pct={min_size_pct!r}: 100 / p must be one of 2, 3, 4, 5, 10, 20")
 
     def turnover_features(self, PM, VOL, so, mcap, lookback=3):
         """csm_turnover_features (src/features.py:60-107, rule T1): (ADV, SH, TURN, TAVG)."""

@@ -851,6 +851,55 @@ int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int
                 int32_t lead, int32_t min_obs, double* RIC, double* PIC, int32_t* NOBS);
 
 /*
+ * Reference-universe breakpoints and universe screens (rules U1..U6 in DESIGN.md section 7): the
+ * qcut edges of each date taken from a subset of its cells -- NYSE breakpoints -- and every ranked
+ * cell of the date (NYSE, AMEX, Nasdaq) assigned to those bins; the edges themselves; and the
+ * price / size screen of the momentum papers (Jegadeesh-Titman 2001: no stock under $5, none under
+ * the smallest NYSE size decile).
+ *
+ * csm_deciles_bp:  M [T_m][N] the signal, NR [T_m][N] (nullable), BP uint8 with row t at
+ *   BP + t * bp_ld: bp_ld = N one row per month, bp_ld = 0 one static row.
+ *   U1  the ranked set of date t is the cells whose M[t][a] is not NaN (the ABSENT payload is a
+ *       NaN); the breakpoint set is the ranked cells with BP[t * bp_ld + a] != 0.  Every byte value
+ *       is data, never an error.
+ *   U2  edges: csm_deciles's rule (qtable, the fp64 lerp without FMA) on the breakpoint set's values
+ *       alone, the distinct edges kept in order.  EDGES [T_m][n_bins + 1]: the NE[t] distinct edges
+ *       first, NaN after them; NE [T_m] int32; NVB [T_m] int32 the size of the breakpoint set.
+ *       -0.0 and 0.0 count as equal.
+ *   U3  NE[t] < 2 (the subset is empty, has one value, or all its values are equal): every label
+ *       of the date is -1.  Otherwise a ranked cell with value x gets #{k in 1..NE-2 : e_k < x},
+ *       an int8 in [0, NE - 2] -- pandas' cut(x, edges, include_lowest=True) inside [e_0, e_last],
+ *       bin 0 below e_0 and bin NE - 2 above e_last.  Non-ranked cells get -1.  With BP all ones
+ *       and n_bins >= 2 the labels are csm_deciles's.
+ *   U4  with NR: EW [T_m][n_bins] the mean of NR over the cells with label d and a non-NaN NR,
+ *       CNT their count, NV [T_m] the ranked cells.  Lane l of 1024 adds its cells l, l + 1024, ...
+ *       in ascending order from 0.0; each of the 16 waves adds its lanes by the halving tree
+ *       (h = 32..1: element j < h += element j + h); the wave sums are added in wave order from
+ *       0.0: a function of N alone.  No floating-point atomic: two calls give the same bits.
+ *   U6  NR is the caller's, as rule N6: the next return of the signal itself.  A screened-out cell
+ *       simply drops from the means.
+ *   n_bins 1..20 without NR, 2/3/4/5/10/20 with.  L, EW, CNT, NV, NVB, EDGES, NE are each
+ *   nullable; L or EDGES is required; with L, NV, EW and CNT all NULL only the edges are computed.
+ *   CSM_E_INVAL: a NULL M, BP or qtable, L and EDGES both NULL, bp_ld not 0 or N, an n_bins
+ *   csm_deciles refuses, T_m < 1, N < 1 or N >= 2^31, T_m * N > 2^40.  Scratch (8 B per cell) is
+ *   the context's group workspace.
+ *
+ * csm_screen:  U5  a cell of M [T_m][N] is kept iff M[t][a] is not NaN, and PM is NULL or
+ *   PM[t][a] >= min_price (a NaN or ABSENT PM fails), and CAP is NULL or CAP[t][a] >= CAPMIN[t]
+ *   (a NaN on either side fails the cell).  MS [T_m][N] = M where kept, NaN elsewhere; KEPT [T_m]
+ *   int32 (nullable) the kept cells.  The screen never changes NR.  CSM_E_INVAL: a NULL M or MS,
+ *   CAP given with a NULL CAPMIN, the size limits above.
+ * +-inf in the data is out of contract.
+ */
+int csm_deciles_bp(csm_ctx* ctx, const double* M, const double* NR, const uint8_t* BP,
+                   int64_t bp_ld, int32_t T_m, int64_t N, int32_t n_bins, const double* qtable,
+                   int8_t* L, double* EW, int32_t* CNT, int32_t* NV, int32_t* NVB, double* EDGES,
+                   int32_t* NE);
+int csm_screen(csm_ctx* ctx, const double* M, const double* PM, double min_price,
+               const double* CAP, const double* CAPMIN, int32_t T_m, int64_t N, double* MS,
+               int32_t* KEPT);
+
+/*
  * Stationary month bootstrap (BASELINE config C5; rule E6): panels b0 .. b0+B-1 of the base
  * month-return panel R[T_m][N] (csm_momentum's R; NaN = no row).  src[B][T_m] int32 out: the
  * source months; PMb[T_m][B][N] out: month prices p0 * prod(1 + r) over the resampled months,
