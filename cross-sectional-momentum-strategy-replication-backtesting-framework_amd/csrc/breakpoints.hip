@@ -24,13 +24,17 @@
 //   U6  NR is the caller's (rule N6); the screen never changes it.
 //
 //   k_bppart   U1.  One workgroup per date, each wave one contiguous chunk of the row: the
-//              breakpoint set's values, in asset order, to the packed row SK; NVB[t].
-//   k_bpedges  U2.  One workgroup per date sorts the NVB[t] packed keys only -- in LDS up to
-//              GD_TILE keys, tiled past that (gsort.h, as k_gdec) -- and takes the n_bins + 1
-//              order statistics with their upper neighbours from the sorted keys.
+//              breakpoint set's values, in asset order, to the packed row SK; NVB[t] (gsort.h's
+//              pack_row).
+//   k_bpedges  U2.  One workgroup per date sorts the NVB[t] packed keys only -- gsort.h's
+//              sort_segment, as k_gdec: in LDS up to the "gdec_small_cap" knob's keys (4,096),
+//              tiled past that; only keys are sorted, so the edges do not depend on the knob --
+//              and takes the n_bins + 1 order statistics with their upper neighbours from the
+//              sorted keys.  The distinct edges are kept in order, NaN after them: this
+//              kernel's own rule, not k_gdec's duplicates='drop'.
 //   k_bplabel  U3, U4.  One workgroup per date: one sweep of the whole row against the at most 19
 //              interior edges (LDS), fused with the decile sums (per-lane registers per label).
-//   k_screen   U5.  One workgroup per date, elementwise, the row's count by an integer tree.
+//   k_screen   U5.  One workgroup per date, elementwise, the row's count by an integer block_sum.
 #include "gsort.h"
 
 #define BP_THREADS 1024
@@ -44,67 +48,35 @@ __global__ __launch_bounds__(BP_THREADS) void k_bppart(const double* __restrict_
                                                        double* __restrict__ SK,
                                                        int32_t* __restrict__ NVB) {
   __shared__ int s_cnt[BP_WAVES];
-  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = blockIdx.x;
   const double* __restrict__ row = M + (int64_t)t * N;
   const uint8_t* __restrict__ bp = BP + (int64_t)t * bp_ld;
-  const int64_t per = ((N + BP_THREADS - 1) / BP_THREADS) * 64;   // cells of one wave's chunk
-  const int64_t i0 = (int64_t)wave * per;
-  const int64_t i1 = i0 + per < N ? i0 + per : N;
-  int c = 0;
-  for (int64_t b = i0; b < i1; b += 64) {   // (wave-uniform trips)
-    const int64_t i = b + lane;
-    bool in = false;
-    if (i < i1) {
-      const double x = row[i];
-      in = x == x && bp[i] != 0;
-    }
-    c += __popcll(__ballot(in));
-  }
-  if (lane == 0) s_cnt[wave] = c;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int w = 0; w < BP_WAVES; ++w) {
-    const int v = s_cnt[w];
-    base += w < wave ? v : 0;
-    tot += v;
-  }
-  if (tid == 0) NVB[t] = tot;
   double* __restrict__ sk = SK + (int64_t)t * N;
-  for (int64_t b = i0; b < i1; b += 64) {
-    const int64_t i = b + lane;
-    double x = qnan();
-    bool in = false;
-    if (i < i1) {
-      x = row[i];
-      in = x == x && bp[i] != 0;
-    }
-    const uint64_t m = __ballot(in);
-    if (in) sk[base + lane_prefix(m)] = x;
-    base += __popcll(m);
-  }
+  double x;   // the cell's value, from the predicate to the emit
+  const int tot = pack_row<BP_THREADS>(
+      N, s_cnt,
+      [&](int64_t i) {
+        x = row[i];
+        return x == x && bp[i] != 0;
+      },
+      [&](int64_t, int pos) { sk[pos] = x; });
+  if (threadIdx.x == 0) NVB[t] = tot;
 }
 
 // ------------------------------------------------------------------------------------ U2
 template <bool SMALL>
 __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_bpedges(
-    int64_t N, int n_bins, QTab qt, const int32_t* __restrict__ NVB, double* SK,
+    int64_t N, int n_bins, QTab qt, int cap, int tile, const int32_t* __restrict__ NVB, double* SK,
     double* __restrict__ EDGES, int32_t* __restrict__ NE) {
   constexpr int NT = SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS;
   __shared__ double s_key[GD_TILE];
   __shared__ double s_edge[MAXQ];
   const int t = blockIdx.x, tid = threadIdx.x;
   const int n = NVB[t];
-  if (SMALL ? n > GD_TILE : n <= GD_TILE) return;   // the other launch's date (block-uniform)
-  double* gk = SK + (int64_t)t * N;
+  if (not_mine<SMALL>(n, cap)) return;
   if (n > 0) {
-    if (SMALL) {
-      for (int p = tid; p < n; p += NT) s_key[p] = gk[p];
-      __syncthreads();
-      tile_sort<NT>(s_key, (uint32_t)n);
-    } else {
-      seg_sort<NT>(gk, s_key, (uint32_t)n, (uint32_t)GD_TILE);
-    }
-    if (tid <= n_bins) s_edge[tid] = qcut_edge(SMALL ? s_key : gk, n, qt.q[tid]);
+    const double* srt = sort_segment<SMALL, NT>(SK + (int64_t)t * N, s_key, n, tile);
+    if (tid <= n_bins) s_edge[tid] = qcut_edge(srt, n, qt.q[tid]);
   }
   __syncthreads();
   if (tid == 0) {   // the distinct edges in order, NaN after them
@@ -182,15 +154,15 @@ __global__ __launch_bounds__(BP_THREADS) void k_bplabel(
   if (NB > 0) {
 #pragma unroll
     for (int d = 0; d < NBS; ++d) {
-      const double sd = gwave_tree(s[d]);
-      const int cd = gwave_tree(c[d]);
+      const double sd = wave_tree(s[d]);
+      const int cd = wave_tree(c[d]);
       if (lane == 0) {
         s_sum[wave][d] = sd;
         s_c[wave][d] = cd;
       }
     }
   }
-  nv = gwave_tree(nv);
+  nv = wave_tree(nv);
   if (lane == 0) s_c[wave][NBS] = nv;
   __syncthreads();
   if (NB > 0 && tid < NB) {
@@ -240,23 +212,11 @@ __global__ __launch_bounds__(BP_THREADS) void k_screen(
     }
   }
   if (!KEPT) return;
-  kept = gwave_tree(kept);
-  if ((tid & 63) == 0) s_k[tid >> 6] = kept;
-  __syncthreads();
-  if (tid == 0) {
-    int k = 0;
-    for (int w = 0; w < BP_WAVES; ++w) k += s_k[w];
-    KEPT[t] = k;
-  }
+  kept = block_sum<int, BP_THREADS>(kept, s_k);
+  if (tid == 0) KEPT[t] = kept;
 }
 
 // ----------------------------------------------------------------------------------- host
-static int bp_dims(csm_ctx* ctx, const char* who, int32_t T_m, int64_t N) {
-  if (T_m < 1 || N < 1 || N > 0x7FFFFFFFLL || (int64_t)T_m > ((int64_t)1 << 40) / N)
-    return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld)", who, T_m, (long long)N);
-  return CSM_OK;
-}
-
 extern "C" {
 
 int csm_deciles_bp(csm_ctx* ctx, const double* M, const double* NR, const uint8_t* BP,
@@ -267,16 +227,13 @@ int csm_deciles_bp(csm_ctx* ctx, const double* M, const double* NR, const uint8_
   int r = prep(ctx);
   if (r) return r;
   if (!M || !BP || !qtable) return set_err(ctx, CSM_E_INVAL, "%s: M, BP or qtable is NULL", who);
-  r = bp_dims(ctx, who, T_m, N);
-  if (r) return r;
+  if (bad_panel(T_m, N, INT32_MAX))
+    return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld)", who, T_m, (long long)N);
   if (bp_ld != 0 && bp_ld != N)
     return set_err(ctx, CSM_E_INVAL, "%s: bp_ld=%lld must be 0 (one static row) or N=%lld", who,
                    (long long)bp_ld, (long long)N);
-  if (n_bins < 1 || n_bins > MAXQ - 1)
-    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d is outside [1, %d]", who, n_bins, MAXQ - 1);
-  if (NR && !nb_dispatch<2, 3, 4, 5, 10, 20>(n_bins, [](auto) {}))
-    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", who,
-                   n_bins);
+  r = check_n_bins(ctx, who, n_bins, NR != nullptr);
+  if (r) return r;
   if (!L && !EDGES) return set_err(ctx, CSM_E_INVAL, "%s: L and EDGES are both NULL", who);
   // the packed keys (8 B per cell), and the edges / counts the caller does not take
   const size_t b_sk = up16((size_t)T_m * (size_t)N * sizeof(double));
@@ -290,17 +247,12 @@ int csm_deciles_bp(csm_ctx* ctx, const double* M, const double* NR, const uint8_
   double* edges = EDGES ? EDGES : (double*)(p + b_sk);
   int32_t* ne = NE ? NE : (int32_t*)(p + b_sk + b_e);
   int32_t* nvb = NVB ? NVB : (int32_t*)(p + b_sk + b_e + b_i);
-  QTab q{};
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
+  const QTab q = qtab_fill(qtable, n_bins);
+  const SortPlan sp = sort_plan();
   const dim3 grid((unsigned)T_m);
   hipLaunchKernelGGL(k_bppart, grid, dim3(BP_THREADS), 0, ctx->stream, M, BP, bp_ld, N, sk, nvb);
   LAUNCH_CHECK(ctx, "k_bppart");
-  hipLaunchKernelGGL(k_bpedges<true>, grid, dim3(GD_SMALL_THREADS), 0, ctx->stream, N, n_bins, q,
-                     nvb, sk, edges, ne);
-  LAUNCH_CHECK(ctx, "k_bpedges (LDS)");
-  hipLaunchKernelGGL(k_bpedges<false>, grid, dim3(GD_LONG_THREADS), 0, ctx->stream, N, n_bins, q,
-                     nvb, sk, edges, ne);
-  LAUNCH_CHECK(ctx, "k_bpedges (tiled)");
+  LAUNCH_PAIR(ctx, k_bpedges, grid, N, n_bins, q, sp.cap, sp.tile, nvb, sk, edges, ne);
   if (!L && !NV && !(NR && (EW || CNT))) return CSM_OK;   // the edges alone
   nb_dispatch<0, 2, 3, 4, 5, 10, 20>(NR ? n_bins : 0, [&](auto nb) {
     hipLaunchKernelGGL(k_bplabel<decltype(nb)::value>, grid, dim3(BP_THREADS), 0, ctx->stream, M,
@@ -317,8 +269,8 @@ int csm_screen(csm_ctx* ctx, const double* M, const double* PM, double min_price
   int r = prep(ctx);
   if (r) return r;
   if (!M || !MS) return set_err(ctx, CSM_E_INVAL, "%s: M or MS is NULL", who);
-  r = bp_dims(ctx, who, T_m, N);
-  if (r) return r;
+  if (bad_panel(T_m, N, INT32_MAX))
+    return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld)", who, T_m, (long long)N);
   if (CAP && !CAPMIN) return set_err(ctx, CSM_E_INVAL, "%s: CAP is given and CAPMIN is NULL", who);
   hipLaunchKernelGGL(k_screen, dim3((unsigned)T_m), dim3(BP_THREADS), 0, ctx->stream, M, PM,
                      min_price, CAP, CAPMIN, N, MS, KEPT);

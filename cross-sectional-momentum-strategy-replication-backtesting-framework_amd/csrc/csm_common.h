@@ -23,6 +23,20 @@ __device__ __forceinline__ double absent_val() { return __longlong_as_double((lo
 __device__ __forceinline__ double qnan() { return __longlong_as_double(0x7FF8000000000000LL); }
 __device__ __forceinline__ bool isnan_d(double x) { return x != x; }
 
+// The halving tree over a wave's 64 lanes (h = 32..1: lane j += lane j + h); lane 0 holds the sum.
+// Rules R1, N3, N4, U4 and I5 name this order.
+template <typename T>
+__device__ __forceinline__ T wave_tree(T v) {
+#pragma unroll
+  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
+  return v;
+}
+
+// A [T_m][N] panel an entry point refuses: an empty side, more than 2^40 cells, or a row of more
+// than n_max cells (the calls that keep 32-bit positions in a row pass 2^31 - 1).
+static inline bool bad_panel(int32_t T_m, int64_t N, int64_t n_max = INT64_MAX) {
+  return T_m < 1 || N < 1 || N > n_max || (int64_t)T_m > ((int64_t)1 << 40) / N;
+}
 
 struct csm_ctx {
   int device;

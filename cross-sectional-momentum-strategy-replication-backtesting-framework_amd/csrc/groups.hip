@@ -4,7 +4,7 @@
 // n_groups is.
 //
 //   k_gpart    N1.  One workgroup per date; each of its GP_WAVES waves owns one contiguous chunk
-//              of the row.  First sweep: per-wave, per-group member counts in LDS (integer adds).
+//              of the row (gsort.h's wave_chunk).  First sweep: per-wave, per-group member counts in LDS (integer adds).
 //              An exclusive prefix over (group, wave) gives the segment offsets SEG[t][g] and each
 //              wave's first slot in each segment.  Second sweep: the members' values and asset
 //              indices go to the packed row SK / SI, group-major and ascending asset inside a
@@ -12,13 +12,15 @@
 //              unhandled lane's id, the ballot of the lanes that share it, mbcnt for the rank --
 //              as many trips as there are distinct groups in the 64 cells.  Cells outside every
 //              group get their -1 / NaN outputs here.
-//   k_gdec     N2, N3.  One workgroup per (date, group).  The segment's keys are sorted by a
-//              bitonic network on exactly n keys (every exchange moves the smaller key down, an
+//   k_gdec     N2, N3.  One workgroup per (date, group).  The segment's keys are sorted by
+//              gsort.h's sort_segment, which k_rank, k_ic and breakpoints.hip's k_bpedges call
+//              too: a bitonic network on exactly n keys (every exchange moves the smaller key down, an
 //              exchange whose upper index is past n is skipped: the network of the next power of
 //              two with +inf above n).  SMALL: a segment of at most `cap` keys, sorted in LDS.
 //              Otherwise: tiles of `tile` keys sorted in LDS, the exchanges wider than a tile made
-//              in the packed row itself.  Each launch returns at once on the other's segments.
-//              Edges are NumPy's lerp on the sorted keys as deciles.inc computes them, deduped;
+//              in the packed row itself.  Each launch returns at once on the other's segments
+//              (not_mine; sort_plan and LAUNCH_PAIR on the host).  Edges are NumPy's lerp on the
+//              sorted keys as deciles.inc computes them, deduped;
 //              a member's label is the count of edges below its value.  Only keys are sorted, so
 //              labels and sums do not depend on which kernel took the segment.  The sums: label
 //              d's wave adds NR over the packed positions lane, lane + 64, ... from 0.0 (0.0
@@ -26,8 +28,8 @@
 //              that depends on the segment's length alone.
 //   k_gpool    N3.  A lane per (date, label) adds the groups' sums and counts, g ascending.
 //   k_gstats   N4, N5.  One workgroup per (date, group): lane sums over positions tid, tid + 256,
-//              ..., the halving tree per wave, the waves in wave order; then the members' adjusted
-//              signals through SI.
+//              ..., the halving tree per wave, the waves in wave order (gsort.h's block_sum);
+//              then the members' adjusted signals through SI.
 //
 // Ranks and information coefficients (rules I1..I6) stand on the same partition and sort:
 //   k_rank     I1, I2.  One workgroup per (date, group), k_gpart's segments (a NULL GID: one group
@@ -35,7 +37,7 @@
 //              le are a lower- and an upper-bound search in the sorted keys, its rank goes out
 //              through SI.  Non-members got their NaN from k_gpart.
 //   k_icpart   I3.  One workgroup per month: the assets with S[t] and Y[t + lead] both not NaN,
-//              in asset order, to an index list and two packed value rows.
+//              in asset order, to an index list and two packed value rows (gsort.h's pack_row).
 //   k_icpearson I5.  k_gstats's sums on the packed values: the means, then the three centred sums.
 //   k_ic       I4.  One workgroup per month.  LDS: S's keys sorted, each position's centred
 //              doubled rank kept as int32, then Y's keys sorted in the same buffer.  Past the cap
@@ -43,7 +45,7 @@
 //              list.  The three sums are int64: exact in any order.
 //
 // No floating-point atomic anywhere: two calls give the same bits.
-#include "gsort.h"   // the wave tree, tile_sort / seg_sort, qcut_edge
+#include "gsort.h"   // block_sum, pack_row / wave_chunk, sort_segment, qcut_edge
 
 #define GP_THREADS 1024
 #define GP_WAVES (GP_THREADS / 64)
@@ -51,13 +53,19 @@
 #define GP_U 4             // steps of 64 cells whose loads a wave issues together
 #define GS_THREADS 256
 
-// segments of at most this many keys take the LDS kernel (csm_tune "gdec_small_cap" lowers it;
-// the other kernel's tile is then twice the next power of two, GD_TILE at most)
+// segments of at most this many keys take the LDS kernels, here and in breakpoints.hip
 static int g_tune_gdec_small_cap = GD_TILE;
 
 static const TuneKnob g_knobs[] = {
     {"gdec_small_cap", &g_tune_gdec_small_cap, [](int v) { return v >= 1 && v <= GD_TILE; }},
 };
+
+SortPlan sort_plan() {
+  const int cap = g_tune_gdec_small_cap;
+  int tile = 2;
+  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  return {cap, tile};
+}
 
 // ------------------------------------------------------------------------------------ N1
 // the group of cell i of the row, -1 for none
@@ -76,9 +84,8 @@ __global__ __launch_bounds__(GP_THREADS) void k_gpart(
   const double* __restrict__ row = S + (int64_t)t * N;
   // (GID NULL: csm_xs_rank's one group of every non-NaN cell)
   const int16_t* __restrict__ gid = GID ? GID + (int64_t)t * g_ld : nullptr;
-  const int64_t per = ((N + GP_THREADS - 1) / GP_THREADS) * 64;   // cells of one wave's chunk
-  const int64_t i0 = (int64_t)wave * per;
-  const int64_t i1 = i0 + per < N ? i0 + per : N;
+  const Chunk ch = wave_chunk<GP_THREADS>(N);
+  const int64_t i0 = ch.i0, i1 = ch.i1;
   for (int k = tid; k < GP_WAVES * GP_MAXG; k += GP_THREADS) (&s_cnt[0][0])[k] = 0;
   __syncthreads();
   for (int64_t b = i0; b < i1; b += 64 * GP_U) {   // GP_U steps of 64 cells, their loads together
@@ -206,21 +213,13 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int seg0 = SEG[(int64_t)t * (n_groups + 1) + g];
   const int n = SEG[(int64_t)t * (n_groups + 1) + g + 1] - seg0;
-  if (SMALL ? n > cap : n <= cap) return;   // the other launch's segment (block-uniform)
+  if (not_mine<SMALL>(n, cap)) return;
   double* gk = SK + (int64_t)t * N + seg0;   // the segment's keys in the packed row
   const uint32_t* __restrict__ si = SI + (int64_t)t * N + seg0;
   const bool ranked = n >= min_group && n > 0;
-  const uint32_t un = (uint32_t)n;
   if (ranked) {
-    if (SMALL) {
-      for (int p = tid; p < n; p += NT) s_key[p] = gk[p];
-      __syncthreads();
-      tile_sort<NT>(s_key, un);
-    } else {
-      seg_sort<NT>(gk, s_key, un, (uint32_t)tile);
-    }
     // edges: NumPy's lerp on the sorted keys, as deciles.inc
-    const double* srt = SMALL ? s_key : gk;
+    const double* srt = sort_segment<SMALL, NT>(gk, s_key, n, tile);
     if (tid <= n_bins) s_edge[tid] = qcut_edge(srt, n, qt.q[tid]);
     __syncthreads();
     if (tid == 0) {   // duplicates='drop'
@@ -270,8 +269,8 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
       s = s + (h ? rr[p] : 0.0);
       c += h ? 1 : 0;
     }
-    s = gwave_tree(s);
-    c = gwave_tree(c);
+    s = wave_tree(s);
+    c = wave_tree(c);
     if (lane == 0) {
       const int64_t o = cell * n_bins + d;
       SUMG[o] = s;
@@ -302,19 +301,6 @@ __global__ __launch_bounds__(64) void k_gpool(const double* __restrict__ SUMG,
 }
 
 // -------------------------------------------------------------------------------- N4, N5
-// lane sums -> one sum: the tree per wave, the waves in wave order from 0.0
-__device__ __forceinline__ double gs_block_sum(double v, double* s_part) {
-  const int tid = threadIdx.x;
-  v = gwave_tree(v);
-  __syncthreads();   // s_part's last readers are done
-  if ((tid & 63) == 0) s_part[tid >> 6] = v;
-  __syncthreads();
-  double r = 0.0;
-#pragma unroll
-  for (int w = 0; w < GS_THREADS / 64; ++w) r = r + s_part[w];
-  return r;
-}
-
 __global__ __launch_bounds__(GS_THREADS) void k_gstats(
     int64_t N, int n_groups, const int32_t* __restrict__ SEG, const uint32_t* __restrict__ SI,
     const double* __restrict__ SK, double* __restrict__ GMEAN, double* __restrict__ GSD,
@@ -330,14 +316,14 @@ __global__ __launch_bounds__(GS_THREADS) void k_gstats(
   const uint32_t* __restrict__ si = SI + (int64_t)t * N + seg0;
   double a = 0.0;
   for (int p = tid; p < n; p += GS_THREADS) a = a + sk[p];
-  const double sum = gs_block_sum(a, s_part);
+  const double sum = block_sum<double, GS_THREADS>(a, s_part);
   const double mean = n > 0 ? sum / (double)n : qnan();
   double q = 0.0;
   for (int p = tid; p < n; p += GS_THREADS) {
     const double d = sk[p] - mean;
     q = q + d * d;
   }
-  const double ss = gs_block_sum(q, s_part);
+  const double ss = block_sum<double, GS_THREADS>(q, s_part);
   const double sd = n >= 2 ? sqrt(ss / (double)(n - 1)) : qnan();
   if (tid == 0) {
     if (GMEAN) GMEAN[cell] = mean;
@@ -402,16 +388,10 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
   const int tid = threadIdx.x;
   const int seg0 = SEG[(int64_t)t * (n_groups + 1) + g];
   const int n = SEG[(int64_t)t * (n_groups + 1) + g + 1] - seg0;
-  if (SMALL ? n > cap : n <= cap) return;   // the other launch's segment (block-uniform)
+  if (not_mine<SMALL>(n, cap)) return;
   double* gk = SK + (int64_t)t * N + seg0;
   const uint32_t* __restrict__ si = SI + (int64_t)t * N + seg0;
-  if (SMALL) {
-    for (int p = tid; p < n; p += NT) s_key[p] = gk[p];
-    __syncthreads();
-    tile_sort<NT>(s_key, (uint32_t)n);
-  } else {
-    seg_sort<NT>(gk, s_key, (uint32_t)n, (uint32_t)tile);
-  }
+  sort_segment<SMALL, NT>(gk, s_key, n, tile);
   Samples sp{};
   if (!SMALL) {
     sp = stage_samples<NT>(gk, n, s_key, GD_TILE);
@@ -430,11 +410,6 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
 
 // -------------------------------------------------------------------------------- I3..I6
 #define IC_THREADS 1024
-__device__ __forceinline__ long long gwave_tree(long long v) {
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
-  return v;
-}
 
 // I3.  One workgroup per month; each wave owns one contiguous chunk of the row.  The assets with
 // S[t] and Y[t + lead] both not NaN go, in asset order, to IX (their indices) and KS / KY (their
@@ -444,7 +419,7 @@ __global__ __launch_bounds__(IC_THREADS) void k_icpart(
     uint32_t* __restrict__ IX, double* __restrict__ KS, double* __restrict__ KY,
     int32_t* __restrict__ CN, int32_t* __restrict__ NOBS) {
   __shared__ int s_cnt[IC_THREADS / 64];
-  const int t = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int t = blockIdx.x, tid = threadIdx.x;
   if ((int64_t)t + lead >= T_m) {   // (block-uniform)
     if (tid == 0) {
       CN[t] = 0;
@@ -454,50 +429,25 @@ __global__ __launch_bounds__(IC_THREADS) void k_icpart(
   }
   const double* __restrict__ rs = S + (int64_t)t * N;
   const double* __restrict__ ry = Y + ((int64_t)t + lead) * N;
-  const int64_t per = ((N + IC_THREADS - 1) / IC_THREADS) * 64;   // cells of one wave's chunk
-  const int64_t i0 = (int64_t)wave * per;
-  const int64_t i1 = i0 + per < N ? i0 + per : N;
-  int c = 0;
-  for (int64_t b = i0; b < i1; b += 64) {   // (wave-uniform trips)
-    const int64_t i = b + lane;
-    bool ok = false;
-    if (i < i1) {
-      const double s = rs[i], y = ry[i];
-      ok = s == s && y == y;
-    }
-    c += __popcll(__ballot(ok));
-  }
-  if (lane == 0) s_cnt[wave] = c;
-  __syncthreads();
-  int base = 0, tot = 0;
-  for (int w = 0; w < IC_THREADS / 64; ++w) {
-    const int v = s_cnt[w];
-    base += w < wave ? v : 0;
-    tot += v;
-  }
-  if (tid == 0) {
-    CN[t] = tot;
-    if (NOBS) NOBS[t] = tot;
-  }
   uint32_t* __restrict__ ix = IX + (int64_t)t * N;
   double* __restrict__ ks = KS + (int64_t)t * N;
   double* __restrict__ ky = KY + (int64_t)t * N;
-  for (int64_t b = i0; b < i1; b += 64) {
-    const int64_t i = b + lane;
-    double s = qnan(), y = qnan();
-    if (i < i1) {
-      s = rs[i];
-      y = ry[i];
-    }
-    const bool ok = s == s && y == y;
-    const uint64_t m = __ballot(ok);
-    if (ok) {
-      const int pos = base + lane_prefix(m);
-      ix[pos] = (uint32_t)i;
-      ks[pos] = s;
-      ky[pos] = y;
-    }
-    base += __popcll(m);
+  double s, y;   // the cell's values, from the predicate to the emit
+  const int tot = pack_row<IC_THREADS>(
+      N, s_cnt,
+      [&](int64_t i) {
+        s = rs[i];
+        y = ry[i];
+        return s == s && y == y;
+      },
+      [&](int64_t i, int pos) {
+        ix[pos] = (uint32_t)i;
+        ks[pos] = s;
+        ky[pos] = y;
+      });
+  if (tid == 0) {
+    CN[t] = tot;
+    if (NOBS) NOBS[t] = tot;
   }
 }
 
@@ -519,8 +469,8 @@ __global__ __launch_bounds__(GS_THREADS) void k_icpearson(
     a = a + ks[p];
     b = b + ky[p];
   }
-  const double ms = gs_block_sum(a, s_part) / (double)n;
-  const double my = gs_block_sum(b, s_part) / (double)n;
+  const double ms = block_sum<double, GS_THREADS>(a, s_part) / (double)n;
+  const double my = block_sum<double, GS_THREADS>(b, s_part) / (double)n;
   double qss = 0.0, qyy = 0.0, qsy = 0.0;
   for (int p = tid; p < n; p += GS_THREADS) {
     const double ds = ks[p] - ms, dy = ky[p] - my;
@@ -528,9 +478,9 @@ __global__ __launch_bounds__(GS_THREADS) void k_icpearson(
     qyy = qyy + dy * dy;
     qsy = qsy + ds * dy;
   }
-  const double css = gs_block_sum(qss, s_part);
-  const double cyy = gs_block_sum(qyy, s_part);
-  const double csy = gs_block_sum(qsy, s_part);
+  const double css = block_sum<double, GS_THREADS>(qss, s_part);
+  const double cyy = block_sum<double, GS_THREADS>(qyy, s_part);
+  const double csy = block_sum<double, GS_THREADS>(qsy, s_part);
   if (tid == 0) PIC[t] = (css > 0.0 && cyy > 0.0) ? csy / sqrt(css * cyy) : qnan();
 }
 
@@ -546,10 +496,10 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
   constexpr int NT = SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS;
   __shared__ double s_key[GD_TILE];
   __shared__ int32_t s_a[SMALL ? GD_TILE : 1];
-  __shared__ long long s_red[NT / 64][3];
+  __shared__ long long s_red[NT / 64];
   const int t = blockIdx.x, tid = threadIdx.x;
   const int n = CN[t];
-  if (SMALL ? n > cap : n <= cap) return;   // the other launch's month (block-uniform)
+  if (not_mine<SMALL>(n, cap)) return;
   if (n < min_obs) {
     if (tid == 0) RIC[t] = qnan();
     return;
@@ -558,17 +508,13 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
   double* ky = KY + (int64_t)t * N;
   long long sab = 0, saa = 0, sbb = 0;
   if (SMALL) {
-    for (int p = tid; p < n; p += NT) s_key[p] = ks[p];
-    __syncthreads();
-    tile_sort<NT>(s_key, (uint32_t)n);
+    sort_segment<SMALL, NT>(ks, s_key, n, tile);
     for (int p = tid; p < n; p += NT) {
       const double x = ks[p];
       s_a[p] = count_to<false>(s_key, 0, n, x) + count_to<true>(s_key, 0, n, x) - n;
     }
     __syncthreads();
-    for (int p = tid; p < n; p += NT) s_key[p] = ky[p];
-    __syncthreads();
-    tile_sort<NT>(s_key, (uint32_t)n);
+    sort_segment<SMALL, NT>(ky, s_key, n, tile);
     for (int p = tid; p < n; p += NT) {
       const double y = ky[p];
       const long long a = s_a[p];
@@ -578,8 +524,8 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
       sbb += b * b;
     }
   } else {
-    seg_sort<NT>(ks, s_key, (uint32_t)n, (uint32_t)tile);
-    seg_sort<NT>(ky, s_key, (uint32_t)n, (uint32_t)tile);
+    sort_segment<SMALL, NT>(ks, s_key, n, tile);
+    sort_segment<SMALL, NT>(ky, s_key, n, tile);
     double* s_ys = s_key + GD_TILE / 2;   // half of the buffer for each row's samples
     const Samples ps = stage_samples<NT>(ks, n, s_key, GD_TILE / 2);
     const Samples py = stage_samples<NT>(ky, n, s_ys, GD_TILE / 2);
@@ -598,24 +544,10 @@ __global__ __launch_bounds__(SMALL ? GD_SMALL_THREADS : GD_LONG_THREADS) void k_
       sbb += b * b;
     }
   }
-  sab = gwave_tree(sab);
-  saa = gwave_tree(saa);
-  sbb = gwave_tree(sbb);
-  if ((tid & 63) == 0) {
-    s_red[tid >> 6][0] = sab;
-    s_red[tid >> 6][1] = saa;
-    s_red[tid >> 6][2] = sbb;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    long long ab = 0, aa = 0, bb = 0;
-    for (int w = 0; w < NT / 64; ++w) {
-      ab += s_red[w][0];
-      aa += s_red[w][1];
-      bb += s_red[w][2];
-    }
-    RIC[t] = (aa > 0 && bb > 0) ? (double)ab / sqrt((double)aa * (double)bb) : qnan();
-  }
+  const long long ab = block_sum<long long, NT>(sab, s_red);
+  const long long aa = block_sum<long long, NT>(saa, s_red);
+  const long long bb = block_sum<long long, NT>(sbb, s_red);
+  if (tid == 0) RIC[t] = (aa > 0 && bb > 0) ? (double)ab / sqrt((double)aa * (double)bb) : qnan();
 }
 
 // ----------------------------------------------------------------------------------- host
@@ -657,7 +589,7 @@ static int grp_reserve(csm_ctx* ctx, const char* who, int32_t T_m, int64_t N, in
 static int grp_check(csm_ctx* ctx, const char* who, const double* S, const int16_t* GID,
                      int64_t g_ld, int32_t T_m, int64_t N, int32_t n_groups,
                      bool gid_opt = false) {
-  if (!S || (!GID && !gid_opt) || T_m < 1 || N < 1 || N > 0x7FFFFFFFLL || (int64_t)T_m > ((int64_t)1 << 40) / N)
+  if (!S || (!GID && !gid_opt) || bad_panel(T_m, N, INT32_MAX))
     return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld)", who, T_m, (long long)N);
   if (n_groups < 1 || n_groups > GP_MAXG)
     return set_err(ctx, CSM_E_INVAL, "%s: n_groups=%d is outside [1, %d]", who, n_groups, GP_MAXG);
@@ -686,33 +618,21 @@ int csm_group_deciles(csm_ctx* ctx, const double* S, const double* NR, const int
   if (!L || !qtable) return set_err(ctx, CSM_E_INVAL, "%s: L or qtable is NULL", who);
   if (min_group < 1)
     return set_err(ctx, CSM_E_INVAL, "%s: min_group=%d must be at least 1", who, min_group);
-  if (n_bins < 1 || n_bins > MAXQ - 1)
-    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d is outside [1, %d]", who, n_bins, MAXQ - 1);
-  if (NR && !nb_dispatch<2, 3, 4, 5, 10, 20>(n_bins, [](auto) {}))
-    return set_err(ctx, CSM_E_INVAL, "%s: n_bins=%d unsupported with NR (use 2,3,4,5,10,20)", who,
-                   n_bins);
+  r = check_n_bins(ctx, who, n_bins, NR != nullptr);
+  if (r) return r;
   GrpWs w;
   r = grp_reserve(ctx, who, T_m, N, n_groups, n_bins, &w);
   if (r) return r;
-  QTab q{};
-  for (int i = 0; i < MAXQ; ++i) q.q[i] = i <= n_bins ? qtable[i] : 1.0;
-  const int cap = g_tune_gdec_small_cap;
-  int tile = 2;
-  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  const QTab q = qtab_fill(qtable, n_bins);
+  const SortPlan sp = sort_plan();
   hipLaunchKernelGGL(k_gpart, dim3((unsigned)T_m), dim3(GP_THREADS), 0, ctx->stream, S, GID, g_ld,
                      N, n_groups, w.seg, w.si, w.sk, L, NVG, NV, (double*)nullptr,
                      (double*)nullptr, (double*)nullptr);
   LAUNCH_CHECK(ctx, "k_gpart");
   const unsigned segs = (unsigned)((int64_t)T_m * n_groups);
   int32_t* cntg = CNTG ? CNTG : w.cntg;
-  hipLaunchKernelGGL(k_gdec<true>, dim3(segs), dim3(GD_SMALL_THREADS), 0, ctx->stream, S, NR, N,
-                     n_groups, n_bins, q, min_group, cap, tile, w.seg, w.si, w.sk, w.sl, L, w.sumg,
-                     cntg, EWG);
-  LAUNCH_CHECK(ctx, "k_gdec (LDS)");
-  hipLaunchKernelGGL(k_gdec<false>, dim3(segs), dim3(GD_LONG_THREADS), 0, ctx->stream, S, NR, N,
-                     n_groups, n_bins, q, min_group, cap, tile, w.seg, w.si, w.sk, w.sl, L, w.sumg,
-                     cntg, EWG);
-  LAUNCH_CHECK(ctx, "k_gdec (tiled)");
+  LAUNCH_PAIR(ctx, k_gdec, segs, S, NR, N, n_groups, n_bins, q, min_group, sp.cap, sp.tile, w.seg,
+              w.si, w.sk, w.sl, L, w.sumg, cntg, EWG);
   if (NR && (EW || CNT)) {
     const int64_t lanes = (int64_t)T_m * n_bins;
     hipLaunchKernelGGL(k_gpool, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, ctx->stream,
@@ -761,20 +681,13 @@ int csm_xs_rank(csm_ctx* ctx, const double* S, const int16_t* GID, int64_t g_ld,
   GrpWs w;
   r = grp_reserve(ctx, who, T_m, N, n_groups, 1, &w);
   if (r) return r;
-  const int cap = g_tune_gdec_small_cap;
-  int tile = 2;
-  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  const SortPlan sp = sort_plan();
   hipLaunchKernelGGL(k_gpart, dim3((unsigned)T_m), dim3(GP_THREADS), 0, ctx->stream, S, GID, g_ld,
                      N, n_groups, w.seg, w.si, w.sk, (int8_t*)nullptr, NVG, (int32_t*)nullptr, RANK,
                      (double*)nullptr, (double*)nullptr);
   LAUNCH_CHECK(ctx, "k_gpart");
-  const unsigned segs = (unsigned)((int64_t)T_m * n_groups);
-  hipLaunchKernelGGL(k_rank<true>, dim3(segs), dim3(GD_SMALL_THREADS), 0, ctx->stream, S, N,
-                     n_groups, method, pct, cap, tile, w.seg, w.si, w.sk, RANK);
-  LAUNCH_CHECK(ctx, "k_rank (LDS)");
-  hipLaunchKernelGGL(k_rank<false>, dim3(segs), dim3(GD_LONG_THREADS), 0, ctx->stream, S, N,
-                     n_groups, method, pct, cap, tile, w.seg, w.si, w.sk, RANK);
-  LAUNCH_CHECK(ctx, "k_rank (tiled)");
+  LAUNCH_PAIR(ctx, k_rank, (unsigned)((int64_t)T_m * n_groups), S, N, n_groups, method, pct,
+              sp.cap, sp.tile, w.seg, w.si, w.sk, RANK);
   return CSM_OK;
 }
 
@@ -783,7 +696,7 @@ int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int
   const char* who = "csm_rank_ic";
   int r = prep(ctx);
   if (r) return r;
-  if (!S || !Y || T_m < 1 || N < 1 || lead < 0)
+  if (!S || !Y || bad_panel(T_m, N) || lead < 0)
     return set_err(ctx, CSM_E_INVAL, "%s: bad arguments (T_m=%d N=%lld lead=%d)", who, T_m,
                    (long long)N, lead);
   if (N > ((int64_t)1 << 20))   // |a| < n <= 2^20: the int64 sums of I4 stay below 2^60
@@ -802,9 +715,7 @@ int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int
   double* ky = (double*)(p + b_k);
   uint32_t* ix = (uint32_t*)(p + 2 * b_k);
   int32_t* cn = (int32_t*)(p + 2 * b_k + b_ix);
-  const int cap = g_tune_gdec_small_cap;
-  int tile = 2;
-  while (tile < 2 * cap && tile < GD_TILE) tile <<= 1;
+  const SortPlan sp = sort_plan();
   hipLaunchKernelGGL(k_icpart, dim3((unsigned)T_m), dim3(IC_THREADS), 0, ctx->stream, S, Y, T_m, N,
                      lead, ix, ks, ky, cn, NOBS);
   LAUNCH_CHECK(ctx, "k_icpart");
@@ -813,14 +724,9 @@ int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int
                        min_obs, cn, ks, ky, PIC);
     LAUNCH_CHECK(ctx, "k_icpearson");
   }
-  if (RIC) {
-    hipLaunchKernelGGL(k_ic<true>, dim3((unsigned)T_m), dim3(GD_SMALL_THREADS), 0, ctx->stream, S,
-                       Y, N, lead, min_obs, cap, tile, cn, ix, ks, ky, RIC);
-    LAUNCH_CHECK(ctx, "k_ic (LDS)");
-    hipLaunchKernelGGL(k_ic<false>, dim3((unsigned)T_m), dim3(GD_LONG_THREADS), 0, ctx->stream, S,
-                       Y, N, lead, min_obs, cap, tile, cn, ix, ks, ky, RIC);
-    LAUNCH_CHECK(ctx, "k_ic (tiled)");
-  }
+  if (RIC)
+    LAUNCH_PAIR(ctx, k_ic, (unsigned)T_m, S, Y, N, lead, min_obs, sp.cap, sp.tile, cn, ix, ks, ky,
+                RIC);
   return CSM_OK;
 }
 

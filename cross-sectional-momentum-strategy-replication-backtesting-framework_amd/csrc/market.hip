@@ -316,8 +316,6 @@ __global__ __launch_bounds__(NX_THREADS) void k_next_ret(const double* __restric
   if (prev >= 0) NR[(int64_t)prev * N + a] = pending_finish(absent_val(), psff);
 }
 
-static inline bool too_big(int32_t T_m, int64_t N) { return (int64_t)T_m > ((int64_t)1 << 40) / N; }
-
 extern "C" {
 
 int csm_tune_market(const char* key, int value) { return tune_set(g_knobs, key, value); }
@@ -326,7 +324,7 @@ int csm_market_factor(csm_ctx* ctx, const double* PM, int32_t T_m, int64_t N, in
                       double* X, double* MKT, int32_t* NMK) {
   int r = prep(ctx);
   if (r) return r;
-  if (!PM || !MKT || T_m < 1 || N < 1 || too_big(T_m, N))
+  if (!PM || !MKT || bad_panel(T_m, N))
     return set_err(ctx, CSM_E_INVAL, "csm_market_factor: bad arguments (T_m=%d N=%lld)", T_m,
                    (long long)N);
   if (min_assets < 1)
@@ -360,7 +358,7 @@ int csm_market_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_
                      double* ALPHA, double* IVOL, double* RESMOM, int32_t* NOBS) {
   int r = prep(ctx);
   if (r) return r;
-  if (!PM || !F || T_m < 1 || N < 1 || too_big(T_m, N))
+  if (!PM || !F || bad_panel(T_m, N))
     return set_err(ctx, CSM_E_INVAL, "csm_market_model: bad arguments (T_m=%d N=%lld)", T_m,
                    (long long)N);
   if (!BETA && !ALPHA && !IVOL && !RESMOM && !NOBS)
@@ -393,7 +391,7 @@ int csm_next_ret(csm_ctx* ctx, const double* PM, const double* S, int32_t T_m, i
                  double* NR) {
   int r = prep(ctx);
   if (r) return r;
-  if (!PM || !S || !NR || T_m < 1 || N < 1 || too_big(T_m, N))
+  if (!PM || !S || !NR || bad_panel(T_m, N))
     return set_err(ctx, CSM_E_INVAL, "csm_next_ret: bad arguments (T_m=%d N=%lld)", T_m,
                    (long long)N);
   hipLaunchKernelGGL(k_next_ret, dim3((unsigned)((N + NX_THREADS - 1) / NX_THREADS)),

@@ -45,18 +45,6 @@ struct XsIn {
 constexpr int xs_n1(int K) { return K + 2; }                    // sw, sy, ss_k
 constexpr int xs_n2(int K) { return (K + 1) * (K + 2) / 2; }    // C_jk (j <= k), c_k, cyy
 
-// R1's tree over the wave's 64 lanes; lane 0 holds the sum.
-__device__ __forceinline__ double wave_tree(double v) {
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_tree(int v) {
-#pragma unroll
-  for (int h = 32; h > 0; h >>= 1) v = v + __shfl_down(v, h, 64);
-  return v;
-}
-
 // The lane sums acc[NS] of a workgroup -> one partial per sum at out[0..NS): R1's tree per wave,
 // then the wave sums in wave order from 0.0.  s_part is [XS_WAVES][NS] of LDS; the trailing
 // barrier lets the next month reuse it.
@@ -401,8 +389,6 @@ __global__ __launch_bounds__(NW_THREADS) void k_newey_west(const double* __restr
   }
 }
 
-static inline bool too_big(int32_t T_m, int64_t N) { return (int64_t)T_m > ((int64_t)1 << 40) / N; }
-
 struct XsWs {
   double* p1;      // [T_m][slices][n1] k_xs_mean's partials
   int32_t* pcnt;   // [T_m][slices] its counts
@@ -440,7 +426,7 @@ int csm_xs_regress(csm_ctx* ctx, const double* Y, const double* const* S, int32_
                    int32_t min_obs, double* GAMMA, double* R2, int32_t* NOBS) {
   int r = prep(ctx);
   if (r) return r;
-  if (!Y || !S || !GAMMA || T_m < 1 || N < 1 || too_big(T_m, N))
+  if (!Y || !S || !GAMMA || bad_panel(T_m, N))
     return set_err(ctx, CSM_E_INVAL, "csm_xs_regress: bad arguments (T_m=%d N=%lld)", T_m,
                    (long long)N);
   if (K < 1 || K > XS_MAXK)

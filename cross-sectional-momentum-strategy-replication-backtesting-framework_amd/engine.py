@@ -48,6 +48,12 @@ def _ptr(t: torch.Tensor | None):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+def _qptr(n_bins: int):
+    """The quantile table as the C calls take it (a table of one entry for an n_bins they refuse)."""
+    q = quantile_table(n_bins) if n_bins >= 1 else np.zeros(1)
+    return q.ctypes.data_as(ctypes.c_void_p)
+
+
 def _need(t: torch.Tensor, name: str, dtype, shape, device):
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch tensor")
@@ -1068,16 +1074,19 @@ class Engine:
                           NT=nw.NT, horizons=hs, lags=lags)
 
     # ------------------------------------------------------------------ within-group sorts
+    def _side_panel(self, X, name, dtypes, T_m, N, what):
+        """A side panel of a [T_m][N] call: [T_m][N] (one row per month) or [N] (static), of one
+        of dtypes; returns (X, its leading dimension: N or 0)."""
+        if not isinstance(X, torch.Tensor) or X.dtype not in dtypes:
+            raise TypeError(f"{name} must be {what}")
+        static = X.dim() == 1
+        _need(X, name, X.dtype, (N,) if static else (T_m, N), self.device)
+        return X, 0 if static else N
+
     def _group_ids(self, GID, T_m, N):
-        """GID as csm_group_* takes it: int16 [T_m][N] (one row per month) or [N] (static);
-        returns (GID, g_ld)."""
-        if not isinstance(GID, torch.Tensor) or GID.dtype != torch.int16:
-            raise TypeError("GID must be an int16 torch tensor (labels: L.to(torch.int16))")
-        if GID.dim() == 1:
-            _need(GID, "GID", torch.int16, (N,), self.device)
-            return GID, 0
-        _need(GID, "GID", torch.int16, (T_m, N), self.device)
-        return GID, N
+        """GID as csm_group_* takes it: int16 [T_m][N] or [N]; returns (GID, g_ld)."""
+        return self._side_panel(GID, "GID", (torch.int16,), T_m, N,
+                                "an int16 torch tensor (labels: L.to(torch.int16))")
 
     def deciles_within(self, S, NR, GID, n_groups, n_bins=10, min_group=1, with_groups=False,
                        with_nv=False):
@@ -1100,10 +1109,9 @@ class Engine:
         EWG = self.empty((T_m, G, nb)) if grp else None
         CNTG = self.empty((T_m, G, nb), torch.int32) if grp else None
         NVG = self.empty((T_m, max(G, 1)), torch.int32) if with_groups else None
-        q = quantile_table(nb) if nb >= 1 else np.zeros(1)
         self._call("csm_group_deciles", _ptr(S), _ptr(NR), _ptr(GID), g_ld, T_m, N, G, nb,
-                   q.ctypes.data_as(ctypes.c_void_p), int(min_group), _ptr(L), _ptr(EW), _ptr(CNT),
-                   _ptr(NV), _ptr(EWG), _ptr(CNTG), _ptr(NVG))
+                   _qptr(nb), int(min_group), _ptr(L), _ptr(EW), _ptr(CNT), _ptr(NV), _ptr(EWG),
+                   _ptr(CNTG), _ptr(NVG))
         out = (L, EW, CNT)
         if with_nv:
             out += (NV,)
@@ -1131,15 +1139,8 @@ class Engine:
                    *(_ptr(o.get(k)) for k in self.GROUP_OUTPUTS))
         return GroupStatsOut(**o)
 
-    def run_neutral(self, P, month_start, GID, n_groups, signal="mom", adjust=None, J=12, skip=1,
-                    n_bins=10, min_group=1, window=12, min_obs=None) -> PipelineOut:
-        """One full pass ranked inside groups (Moskowitz-Grinblatt 1999).  The signal is built as
-        run (signal "mom") or run_signal (its names) build it.  adjust None: labels by
-        deciles_within, the decile means pooled over the groups.  adjust "demean" / "zscore": the
-        signal minus its group's mean (over its deviation), rule N5, then a plain deciles on it.
-        M is the signal ranked and NR the signal's next return (rule N6)."""
-        if adjust not in (None, "demean", "zscore"):
-            raise ValueError(f"adjust must be None, 'demean' or 'zscore', got {adjust!r}")
+    def _signal_panels(self, P, month_start, signal, J, skip, n_bins, window, min_obs):
+        """(PM, S, NR) of a signal name: "mom" as run builds it, the others as run_signal does."""
         if signal == "mom":
             PM, _ = self.month_end(P, month_start)
             T_m, N = PM.shape
@@ -1150,6 +1151,18 @@ class Engine:
         else:
             r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs)
             PM, S, NR = r.PM, r.M, r.NR
+        return PM, S, NR
+
+    def run_neutral(self, P, month_start, GID, n_groups, signal="mom", adjust=None, J=12, skip=1,
+                    n_bins=10, min_group=1, window=12, min_obs=None) -> PipelineOut:
+        """One full pass ranked inside groups (Moskowitz-Grinblatt 1999).  The signal is built as
+        run (signal "mom") or run_signal (its names) build it.  adjust None: labels by
+        deciles_within, the decile means pooled over the groups.  adjust "demean" / "zscore": the
+        signal minus its group's mean (over its deviation), rule N5, then a plain deciles on it.
+        M is the signal ranked and NR the signal's next return (rule N6)."""
+        if adjust not in (None, "demean", "zscore"):
+            raise ValueError(f"adjust must be None, 'demean' or 'zscore', got {adjust!r}")
+        PM, S, NR = self._signal_panels(P, month_start, signal, J, skip, n_bins, window, min_obs)
         if adjust is None:
             L, EW, CNT, NV = self.deciles_within(S, NR, GID, n_groups, n_bins, min_group,
                                                  with_nv=True)
@@ -1164,14 +1177,8 @@ class Engine:
     def _bp_mask(self, BP, T_m, N):
         """BP as csm_deciles_bp takes it: uint8 (or bool, reinterpreted) [T_m][N] (one row per
         month) or [N] (static); returns (BP, bp_ld)."""
-        if not isinstance(BP, torch.Tensor) or BP.dtype not in (torch.uint8, torch.bool):
-            raise TypeError("BP must be a uint8 or bool torch tensor")
-        if BP.dim() == 1:
-            _need(BP, "BP", BP.dtype, (N,), self.device)
-            ld = 0
-        else:
-            _need(BP, "BP", BP.dtype, (T_m, N), self.device)
-            ld = N
+        BP, ld = self._side_panel(BP, "BP", (torch.uint8, torch.bool), T_m, N,
+                                  "a uint8 or bool torch tensor")
         return (BP.view(torch.uint8) if BP.dtype == torch.bool else BP), ld
 
     def deciles_bp(self, M, NR, BP, n_bins=10, with_nv=False, with_edges=False):
@@ -1193,10 +1200,8 @@ class Engine:
         NVB = self.empty((T_m,), torch.int32) if with_nv else None
         EDGES = self.empty((T_m, max(nb, 0) + 1)) if with_edges else None
         NE = self.empty((T_m,), torch.int32) if with_edges else None
-        q = quantile_table(nb) if nb >= 1 else np.zeros(1)
-        self._call("csm_deciles_bp", _ptr(M), _ptr(NR), _ptr(BP), ld, T_m, N, nb,
-                   q.ctypes.data_as(ctypes.c_void_p), _ptr(L), _ptr(EW), _ptr(CNT), _ptr(NV),
-                   _ptr(NVB), _ptr(EDGES), _ptr(NE))
+        self._call("csm_deciles_bp", _ptr(M), _ptr(NR), _ptr(BP), ld, T_m, N, nb, _qptr(nb),
+                   _ptr(L), _ptr(EW), _ptr(CNT), _ptr(NV), _ptr(NVB), _ptr(EDGES), _ptr(NE))
         out = (L, EW, CNT)
         if with_nv:
             out += (NV, NVB)
@@ -1215,10 +1220,8 @@ class Engine:
         EDGES = self.empty((T_m, max(nb, 0) + 1))
         NE = self.empty((T_m,), torch.int32)
         NVB = self.empty((T_m,), torch.int32)
-        q = quantile_table(nb) if nb >= 1 else np.zeros(1)
-        self._call("csm_deciles_bp", _ptr(S), None, _ptr(BP), ld, T_m, N, nb,
-                   q.ctypes.data_as(ctypes.c_void_p), None, None, None, None, _ptr(NVB),
-                   _ptr(EDGES), _ptr(NE))
+        self._call("csm_deciles_bp", _ptr(S), None, _ptr(BP), ld, T_m, N, nb, _qptr(nb), None,
+                   None, None, None, _ptr(NVB), _ptr(EDGES), _ptr(NE))
         return EDGES, NE, NVB
 
     def screen(self, M, PM=None, min_price=None, CAP=None, CAPMIN=None, with_kept=False):
@@ -1253,16 +1256,7 @@ class Engine:
         smallest quintile).  M is the screened signal and NR the signal's next return (rule U6)."""
         if (CAP is None) != (min_size_pct is None):
             raise ValueError("CAP and min_size_pct go together")
-        if signal == "mom":
-            PM, _ = self.month_end(P, month_start)
-            T_m, N = PM.shape
-            if self.default_chunks(T_m, N, J, skip) > 1:
-                _, S, NR = self.momentum_chunked(PM, J, skip)
-            else:
-                _, S, NR = self.momentum(PM, J, skip)
-        else:
-            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs)
-            PM, S, NR = r.PM, r.M, r.NR
+        PM, S, NR = self._signal_panels(P, month_start, signal, J, skip, n_bins, window, min_obs)
         T_m, N = S.shape
         if BP is None:
             BP = torch.ones((N,), dtype=torch.uint8, device=self.device)

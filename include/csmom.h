@@ -783,7 +783,8 @@ int csm_newey_west(csm_ctx* ctx, const double* G, int32_t T, int32_t C, int64_t 
  *       without a decile afterwards (run_demo.py:41-49), so cells without a group simply drop out
  *       of the means.
  * "gdec_small_cap" (csm_tune, 1..4096) moves the segment length at which the LDS sort hands over
- * to the tiled one; labels, counts and sums do not depend on it.
+ * to the tiled one, here, in csm_xs_rank, csm_rank_ic and csm_deciles_bp; labels, counts, sums,
+ * ranks and edges do not depend on it.
  *
  * csm_group_stats: N4  GCNT [T_m][n_groups] int32 the member count n; GMEAN = (sum of S over the
  *       members) / n, NaN for n = 0: lane l of 256 adds positions l, l + 256, ... from 0.0, each
@@ -882,7 +883,8 @@ int csm_rank_ic(csm_ctx* ctx, const double* S, const double* Y, int32_t T_m, int
  *   nullable; L or EDGES is required; with L, NV, EW and CNT all NULL only the edges are computed.
  *   CSM_E_INVAL: a NULL M, BP or qtable, L and EDGES both NULL, bp_ld not 0 or N, an n_bins
  *   csm_deciles refuses, T_m < 1, N < 1 or N >= 2^31, T_m * N > 2^40.  Scratch (8 B per cell) is
- *   the context's group workspace.
+ *   the context's group workspace.  "gdec_small_cap" moves the LDS / tiled hand-over of the
+ *   breakpoint set's sort too; the edges do not depend on it.
  *
  * csm_screen:  U5  a cell of M [T_m][N] is kept iff M[t][a] is not NaN, and PM is NULL or
  *   PM[t][a] >= min_price (a NaN or ABSENT PM fails), and CAP is NULL or CAP[t][a] >= CAPMIN[t]

@@ -67,6 +67,9 @@ def main():
         calls[f"loop over groups G={G}"] = lambda gid2=gid2, G=G: loop(gid2, G)
         calls[f"group_stats G={G}"] = lambda gid=gid, G=G: eng.group_stats(S, gid, G)
     calls["deciles (one sort)"] = lambda: eng.deciles(S, NR, nb)
+    bp = torch.rand((N,), generator=gen, device=dev) < 0.3   # a static 30 % breakpoint subset
+    calls["deciles_bp"] = lambda: eng.deciles_bp(S, NR, bp, nb)
+    calls["breakpoints"] = lambda: eng.breakpoints(S, bp, nb)
     # the two routes agree before they are timed
     for G in args.groups:
         a = eng.deciles_within(S, NR, gids[G], G, nb)[0]

@@ -11,7 +11,8 @@ ref's Kahan sums in asset order.  Two calls give the same bits.
 
 The kernels have one hand-over length: a breakpoint set of at most 4,096 values is sorted in LDS,
 a larger one in tiles; test_handover_lengths puts sets of 4,095, 4,096, 4,097 and 8,193 values on
-its dates.
+its dates.  csm_tune "gdec_small_cap" lowers that length; test_lowered_cap runs the tiled sort
+with several tiles on 1,000-asset rows at a cap of 64.
 
 Every parametrised case asserts that at least half of its ranked cells carry a label >= 0 in the
 ref, so nothing passes on -1s; the named degenerate cases assert exactly their degenerate output.
@@ -153,6 +154,41 @@ def test_handover_lengths(engine):
     ref = ref_case("handover", M, NR, BP, nb)
     assert ref["NVB"].tolist() == [4095, 4096, 4097, 8193] and half_labelled(ref, M)
     check_bp(engine, M, NR, BP, nb, ref)
+
+
+def lowered_cap_cases():
+    """(name, M, NR, BP, n_bins) of test_lowered_cap."""
+    M, NR, BP = make_case(3, 1000, True, seed=7, nan=0.1)    # about 270 breakpoint cells a date
+    yield "static", M, NR, BP, 10
+    T_m, N = 4, 1000
+    M, NR, _ = make_case(T_m, N, False, seed=6)
+    BP = np.zeros((T_m, N), dtype=np.uint8)
+    rng = np.random.default_rng(7)
+    for t, k in enumerate((64, 65, 128, 129)):
+        BP[t, rng.choice(np.nonzero(~np.isnan(M[t]))[0], size=k, replace=False)] = 255
+    yield "handover", M, NR, BP, 10
+
+
+def test_lowered_cap(engine):
+    """gdec_small_cap = 64: k_bpedges follows the knob, so about 270 breakpoint cells a date are
+    three 128-key tiles merged through the packed row, and sets of 64 / 65 / 128 / 129 cells are
+    the hand-over, a one-tile and a two-tile tiled sort.  Exact against the ref, and every output
+    bit for bit what the default cap gives."""
+    for name, M, NR, BP, nb in lowered_cap_cases():
+        ref = ref_case(("cap64", name), M, NR, BP, nb)
+        assert half_labelled(ref, M)
+        if name == "handover":
+            assert ref["NVB"].tolist() == [64, 65, 128, 129]
+        else:
+            assert ((ref["NVB"] > 256) & (ref["NVB"] <= 384)).all()
+        at_default = check_bp(engine, M, NR, BP, nb, ref)
+        assert engine.lib.csm_tune(b"gdec_small_cap", 64) == 0
+        try:
+            at_64 = check_bp(engine, M, NR, BP, nb, ref)
+        finally:
+            assert engine.lib.csm_tune(b"gdec_small_cap", 4096) == 0
+        for a, b in zip(at_64, at_default):
+            assert torch.equal(a.view(torch.uint8), b.view(torch.uint8))
 
 
 def test_inner_subset_leaves_both_tails_outside(engine):
