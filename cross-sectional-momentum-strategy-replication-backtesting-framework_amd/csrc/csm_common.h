@@ -156,7 +156,46 @@ static inline hipError_t zero_i32_async(int32_t* p, int n, hipStream_t st) {
   return hipGetLastError();
 }
 
-// ---- shared by the decile kernels (csmom.hip and deciles_narrow.hip) -------------------------
+// ---- calls between the engine's sources -------------------------------------------------------
+// A kernel is defined in one source, beside every host function that takes its address; another
+// source launches it through one of these.
+// Each stage's csm_tune table (the knob variables are static in the stage's source); csm_tune and
+// csm_tune_ptr (context.hip) try them in turn.
+int csm_tune_scans(const char* key, int value);       // scans.hip
+int csm_tune_signal(const char* key, int value);      // signal.hip
+int csm_tune_signal_tc(const char* key, int value);   // signal_tc.hip
+int csm_tune_deciles(const char* key, int value);     // deciles_wide.hip
+int csm_tune_ptr_deciles(const char* key, void* p);
+int csm_tune_shards(const char* key, int value);      // shards.hip
+extern "C" {   // (these five are among the library's exported symbols)
+int csm_tune_portfolio(const char* key, int value);   // portfolio.hip
+int csm_tune_ptr_portfolio(const char* key, void* p);
+int csm_tune_signals(const char* key, int value);     // signals.hip
+int csm_tune_market(const char* key, int value);      // market.hip
+int csm_tune_groups(const char* key, int value);      // groups.hip
+}
+// The fused month-end + scan launch behind every csm_signal* entry point and csm_pipeline
+// (signal.hip): k_signal_tail or k_signal for the panel's width and alignment and the signal
+// knobs.  sh: a date-shard pass (carry_out is the shard's end-state record); ids: the decile
+// pass's bucket ids, or NULL; halo: the fused halo prologue's arguments, or NULL.
+struct HaloArgs;
+int signal_launch(csm_ctx* ctx, const char* who, const double* P, int64_t T_d, int64_t N,
+                  const int64_t* month_start, int32_t T_m, int32_t max_month_days, int32_t J,
+                  int32_t skip, double* PM, double* R, double* M, double* NR, const double* carry,
+                  const double* next_pm, double* carry_out, bool sh = false,
+                  uint16_t* ids = nullptr, const HaloArgs* halo = nullptr);
+// The exchange records of G month chunks of a [T_m][N] month-price panel, out [G][6 + T][N], and
+// their fold into each chunk's carry (g < 0: every chunk, outputs stacked per chunk; else chunk g
+// alone) -- shards.hip's k_shard_summary_chunked and k_fold_carry, which the time-chunked scans
+// of scans.hip launch too.  The caller checks the launch (LAUNCH_CHECK).
+struct FoldJs;
+void launch_shard_summary_chunked(hipStream_t st, const double* PM, int T_m, int64_t N, int T,
+                                  int G, double* out);
+void launch_fold_carry(hipStream_t st, const double* sm, int G, int g, int64_t N, int J, int skip,
+                       double* carry, double* next_pm, const double* tail_pm, const FoldJs& jq,
+                       double* psq);
+
+// ---- shared by the decile kernels (deciles_wide.hip and deciles_narrow.hip) ------------------
 #define MAXQ 21  // n_bins + 1 <= 21
 #define MAXT 42  // distinct target ranks (2 per interior quantile + min + max)
 // Phase timestamps (profiling aid, csm_tune_ptr("dec_timing", buf)): per date row, wall-clock
@@ -201,7 +240,7 @@ __device__ __forceinline__ uint32_t csm_fid(double x) {
 }
 
 // The split decile pass on ids (deciles.inc, wide rows): device workspace of the plan / sweep /
-// finish launches, carved from the context's split buffer (csmom.hip dsplit_layout).  A chunk is
+// finish launches, carved from the context's split buffer (deciles_wide.hip dsplit_layout).  A chunk is
 // a whole number of the merged pass's sweep trips (SPLIT_TRIP cells: 512 lanes x 4 groups x 4
 // cells), and a sweep workgroup's lane owns the cells the merged pass's lane of that index owns
 // there, so both passes sum next_ret in the same order (deciles.inc DEC_CHUNK_ORDER).
@@ -234,7 +273,7 @@ static inline bool nb_dispatch(int n_bins, F&& f) {
   return ((n_bins == NBs && (f(std::integral_constant<int, NBs>{}), true)) || ...);
 }
 
-// The arguments of one decile pass, filled once by csmom.hip's deciles_dispatch and unpacked
+// The arguments of one decile pass, filled once by deciles_wide.hip's deciles_dispatch and unpacked
 // into k_deciles's parameters at each launch (dec_launch).  A field the pass does not use is NULL.
 struct DecLaunch {
   int T_m;            // date rows: one workgroup each

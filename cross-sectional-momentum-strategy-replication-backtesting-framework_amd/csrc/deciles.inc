@@ -1,4 +1,4 @@
-// deciles.inc -- the per-date qcut kernel (k_deciles), included by csmom.hip (wide rows:
+// deciles.inc -- the per-date qcut kernel (k_deciles), included by deciles_wide.hip (wide rows:
 // DEC_THREADS 512, HB 8192 buckets, CAP 4096 candidates; 8192 rather than 4096 buckets halves
 // the target-bucket populations and cut C4's selection + gather time by a third) and by
 // deciles_narrow.hip (rows of a few thousand assets: 256 threads, 1024 buckets, 2048

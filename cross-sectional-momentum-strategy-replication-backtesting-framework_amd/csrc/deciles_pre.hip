@@ -1,7 +1,7 @@
 // deciles_pre.hip -- the per-date qcut kernel of the fused pipeline (csm_deciles_ids /
 // csm_pipeline): the wide-row kernel of csrc/deciles.inc in PRE mode, reading the fixed-map
 // bucket ids csm_signal_ids wrote (M is read only for the few cells near a bin edge).  Its own
-// translation unit so the kernel builds in parallel with csmom.hip.
+// translation unit so the kernel builds in parallel with the other sources.
 #include "csm_common.h"
 
 // (overridable for same-box A/B builds: -DDEC_PRE_THREADS=256 -DDEC_PRE_HB=4096 ...)
@@ -26,7 +26,7 @@ namespace dec_pre {
 bool launch_deciles_pre(const DecLaunch& a, int64_t cells) {
   // merged pass first (flg): one sweep of ids + next_ret per row (deciles.inc, MG); then the
   // general kernel takes the rows it left (all rows without flg) -- and, LS given, its last
-  // workgroup forms the long-short (csmom.hip launches k_long_short instead for these rows).
+  // workgroup forms the long-short (deciles_wide.hip launches k_long_short instead for these rows).
   // (The merged pass with the general path as an in-workgroup fallback needs more than the 128
   // VGPRs of two 512-thread workgroups per CU at this width.)
   // (the merged pass sums in the split pass's order: its chunks of `cells` cells)

@@ -1,5 +1,6 @@
 // scan.h -- the per-asset momentum scan's month step, stated once (oracle/csmom_oracle.py,
-// momentum_scan) in pieces that the scan kernels of csmom.hip and sweep_boot.hip compose:
+// momentum_scan) in pieces that the scan kernels of scans.hip, signal.hip, signal_tc.hip,
+// shards.hip and sweep_boot.hip compose:
 //   price_step            forward-fill + one-month return of a present row
 //   lds_push / lds_prod   the J + skip ring of factors fl(1 + ret) in LDS
 //   reg_push / reg_prod   the same ring as a register shift ring, oldest first
@@ -8,6 +9,9 @@
 //   scan_step_on          the whole step of one asset with its stores, on a given ring policy
 //   pending_finish        the last pending row's next_ret at the end of a scan
 //   store_pair / store_next_ret_pair   two adjacent assets' outputs as 16-B stores
+//   scan_step / scan_step_pair / scan_step_reg   scan_step_on at its sites: the LDS ring, two
+//                         adjacent assets with paired stores, the register ring
+//   scan_shadow           the step's state transition alone, no output
 // Every product runs oldest factor first, left to right, then - 1.0: every composition gives the
 // same bits.  Absent rows (no step at all) and the output stores stay with the sites and with
 // scan_step_on.
@@ -250,4 +254,95 @@ __device__ __forceinline__ void chunk_range(int T_m, int G, int g, int& m0, int&
   const int base = T_m / G, rem = T_m % G;
   m0 = g * base + (g < rem ? g : rem);
   m1 = m0 + base + (g < rem ? 1 : 0);
+}
+
+// =====================================================================================
+// The month step's sites with an LDS ring (shared by k_momentum and k_signal): scan_step_on
+// with the LDS ring policy, and its form for two adjacent assets.
+// =====================================================================================
+template <int JC = 0>
+__device__ __forceinline__ double scan_step(ScanLane& s, double x, int m, double* ring, int RS,
+                                            int W, int J, int64_t N, int64_t a,
+                                            double* __restrict__ R, double* __restrict__ M,
+                                            double* __restrict__ NR) {
+  return scan_step_on(s, x, m, N, a, R, M, NR,
+                      [&](double fct) { return lds_push_mom<JC>(s, ring, RS, W, J, fct); });
+}
+
+// scan_step for two adjacent assets a0, a0 + 1 (a0 even) with their stores paired: mom_J
+// (and ret_1m) as one 16-B store per row, next_ret as one 16-B store when both assets write
+// the same row (the steady state), so a wave issues half the store instructions.  Same
+// arithmetic in the same order as two scan_step calls: bit-identical outputs.
+template <int JC = 0>
+__device__ __forceinline__ void scan_step_pair(ScanLane (&s)[2], const double (&x)[2], int m,
+                                               double* ring0, int RS, int W, int J, int64_t N,
+                                               int64_t a0, double* __restrict__ R,
+                                               double* __restrict__ M, double* __restrict__ NR,
+                                               double (&mom)[2]) {
+  const double NaN = qnan();
+  double ret[2];
+  int wp[2];          // next_ret row of the pending ranked row (-1: none)
+  double vp[2];
+  bool wc[2];         // NaN next_ret at row m
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    wp[c] = -1;
+    vp[c] = NaN;
+    if (is_absent(x[c])) {
+      ret[c] = NaN; mom[c] = NaN; wc[c] = true;
+      continue;
+    }
+    ret[c] = price_step(x[c], s[c].pff);
+    mom[c] = lds_push_mom<JC>(s[c], ring0 + c, RS, W, J, 1.0 + ret[c]);
+    // rank_step's update restated at the site (its arithmetic, ffill and subset_ret, is shared):
+    // through any function form the 512-VGPR one-wave k_signal variants spill more than they do
+    // with these statements inline
+    const bool ranked = !isnan_d(mom[c]);
+    const double ps_new = ffill(x[c], s[c].psff);
+    if (s[c].prev >= 0) { wp[c] = s[c].prev; vp[c] = subset_ret(ps_new, s[c].psff); }
+    if (ranked) {
+      s[c].psff = ps_new;
+      s[c].prev = m;
+      wc[c] = false;
+    } else {
+      s[c].prev = -1;
+      wc[c] = true;
+    }
+  }
+  const int64_t o = (int64_t)m * N + a0;
+  if (R) store_pair(R + o, ret[0], ret[1]);
+  store_pair(M + o, mom[0], mom[1]);
+  store_next_ret_pair(NR, N, a0, o, wp, vp, wc);
+}
+
+// scan_step without outputs (the state transition only): the step of a trajectory that is
+// followed but not written, such as the speculative one (F) beside k_shard_repair's true one.
+__device__ __forceinline__ void scan_shadow(ScanLane& s, double x, int m, double* ring, int RS,
+                                            int W, int J) {
+  if (is_absent(x)) return;
+  const double ret = price_step(x, s.pff);
+  const double mom = lds_push_mom(s, ring, RS, W, J, 1.0 + ret);
+  rank_step(x, mom, m, s.psff, s.prev, [](int, double) {});
+}
+
+// A lane's row value of VEC adjacent assets (one double, or a double2 of a 16-B load) and its
+// component k.
+template <int VEC> struct RowT;
+template <> struct RowT<1> { typedef double T; };
+template <> struct RowT<2> { typedef double2 T; };
+__device__ __forceinline__ double comp(double v, int) { return v; }
+__device__ __forceinline__ double comp(double2 v, int k) { return k == 0 ? v.x : v.y; }
+
+// scan_step with the ring in registers, oldest first (the same factors, product order and
+// stores as scan_step's LDS ring).  JC > 0: J is the compile-time JC (the product's factor
+// count folds: no per-factor select).
+template <int WR, int JC = 0>
+__device__ __forceinline__ double scan_step_reg(ScanLane& s, double x, int m, double (&fr)[WR],
+                                                int J, int64_t N, int64_t a,
+                                                double* __restrict__ R, double* __restrict__ M,
+                                                double* __restrict__ NR) {
+  return scan_step_on(s, x, m, N, a, R, M, NR, [&](double fct) {
+    reg_push(fr, fct);
+    return reg_prod(fr, JC > 0 ? JC : J) - 1.0;
+  });
 }

@@ -391,6 +391,51 @@ def test_halo_shards_sparse_panel(engine, G, H, cols_wg, fold_repair):
     assert cnt > 0
 
 
+@pytest.mark.parametrize("cols_wg", [1, 0])
+def test_summary_cols_neutral_record_past_64_rows(engine, cols_wg):
+    """csm_shard_summary_cols with J + skip = 58: the record has 65 rows, one more than the 64
+    threads of the workgroup that writes a column.  The listed column is the oracle's record of
+    that asset's month prices, and every column past the list's count is the oracle's record of an
+    asset with no present month -- all 65 rows of it, bit for bit (the ABSENT payload too), over
+    a buffer that held a finite sentinel."""
+    from oracle.synth_np import make_panel
+    J, skip, a, cap = 57, 1, 5, 4
+    S = 6 + J + skip + 1
+    assert S == 65
+    pan = make_panel(8, 1310, seed=23, nan_day=0.05, absent_month=0.03, nan_month=0.05,
+                     cents=True)
+    P, ms = pan["P"], pan["month_start"].astype(np.int64)
+    T_m = len(ms) - 1
+    assert 60 <= T_m <= 64
+    PM, _, _, _, st = engine.signal_shard(_up(P), _up(ms), int(np.diff(ms).max()), J, skip)
+    idx = torch.tensor([a, 0, 0, 0], dtype=torch.int32, device="cuda:0")
+    cnt = torch.tensor([1], dtype=torch.int32, device="cuda:0")
+    out = torch.full((S, cap), 12345.0, dtype=torch.float64, device="cuda:0")
+    lib = engine.lib
+    try:
+        assert lib.csm_tune(b"cols_wg", cols_wg) == 0
+        engine.shard_summary_cols(PM, st, idx, cnt, J, skip, out=out)
+        got = out.cpu().numpy()
+    finally:
+        lib.csm_tune(b"cols_wg", 1)
+    pm = O.month_end(P, ms)[0]
+    ref = np.empty((S, cap))
+    ref[:, :1] = O.shard_summary(pm[:, a:a + 1], J, skip)
+    ref[:, 1:] = O.shard_summary(O.absent_like((T_m, cap - 1)), J, skip)
+    assert np.array_equal(got.view(np.int64), ref.view(np.int64))
+
+
+def test_shard_summary_of_no_month(engine):
+    """csm_shard_summary accepts T_m = 0: every asset gets the record with no present month."""
+    from csmom.engine import _ptr
+    J, skip, N = 12, 1, 300
+    PM = engine.empty((1, N))
+    out = torch.full((6 + J + skip + 1, N), 12345.0, dtype=torch.float64, device="cuda:0")
+    engine._call("csm_shard_summary", _ptr(PM), 0, N, J, skip, _ptr(out))
+    ref = O.shard_summary(np.empty((0, N)), J, skip)
+    assert np.array_equal(out.cpu().numpy().view(np.int64), ref.view(np.int64))
+
+
 @pytest.mark.parametrize("G", [2, 7])
 @pytest.mark.parametrize("j12", [1, 0])
 def test_halo_shards_four_wave_blocks(engine, G, j12):
