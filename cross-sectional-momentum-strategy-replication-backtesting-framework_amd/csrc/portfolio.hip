@@ -1994,6 +1994,14 @@ void launch_bootstrap_index(hipStream_t st, int T_m, int B, int64_t b0, uint64_t
 static int g_tune_cohort_lds = 1;
 // 1: label-sorted segment gathers (k_label_sort + k_cohort_seg) where N <= SEG_MAXN
 static int g_tune_cohort_seg = 1;
+// Whether the cohort pass of (N, Kmax, n_bins) takes the label-sorted segment path.  The ONE
+// test of it: the chunk plan (pf_plan), the per-panel launcher (launch_cohort), the leg bitplanes
+// (legs_masks) and the shared-return entries (csm_cohort_sums_js*) all ask here, so every entry
+// sums a panel through the same kernel and gives it the same bits.  (The shared-return pass has
+// a bound of its own on top: its nJ offset tables share the LDS table of SEG_MAXKD entries.)
+static bool seg_path(int64_t N, int64_t Kmax, int n_bins) {
+  return g_tune_cohort_seg && N <= SEG_MAXN && Kmax * (n_bins + 1) <= SEG_MAXKD;
+}
 // workgroups of the persistent general-row turnover launch (walking the work list)
 static int g_tune_turn_gen_grid = 8192;   // C5 portfolio: 512 49.1, 2048 40.1, 8192 39.5 ms
 // 1: k_overlap_rows (one thread per (t, b, decile) serving every K of the set) for single-chunk
@@ -2057,7 +2065,7 @@ static PfPlan pf_plan(int32_t T_m, int32_t B, int64_t N, int32_t K, int32_t n_bi
   // the label-sorted segment path (launch_cohort) owns every segment whole in one of its first
   // ceil(1024 / rows) chunks and writes zeros in the others: plan only those (C3: 4 -> 1 chunk,
   // a quarter of the cohort workgroups and overlap partials; the sums are the same bits)
-  if (g_tune_cohort_seg && N <= SEG_MAXN && (int64_t)K * (n_bins + 1) <= SEG_MAXKD) {
+  if (seg_path(N, K, n_bins)) {
     const int64_t cs = (1024 + rows - 1) / rows;
     C = C < cs ? C : (cs < 1 ? 1 : cs);
   }
@@ -2203,7 +2211,7 @@ static void launch_cohort_seg(const CohortLaunch& a, const int8_t* L, char* ws) 
 // segment pass ran (its partials in the two-leg layout).
 template <int NB>
 static bool launch_cohort(const CohortLaunch& a, const int8_t* L, char* ws) {
-  if (g_tune_cohort_seg && a.lay.seg && a.K * (NB + 1) <= SEG_MAXKD) {
+  if (seg_path(a.N, a.K, NB)) {
     (a.legs ? (a.W ? launch_cohort_seg<NB, true, true> : launch_cohort_seg<NB, false, true>)
             : (a.W ? launch_cohort_seg<NB, true, false> : launch_cohort_seg<NB, false, false>))(a, L, ws);
     return a.legs;
@@ -2346,9 +2354,10 @@ int csm_cohort_sums_js(csm_ctx* ctx, int32_t nJ, const int8_t* const* L, const d
   const PfLayout& lay = a.lay;
   char* ws[SEG_MAXJ];
   for (int q = 0; q < nJ; ++q) ws[q] = (char*)workspaces[q];
-  // one staged return row for every J: the segment path with one chunk per row; otherwise the
-  // per-J passes (the same partials)
-  const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 &&
+  // one staged return row for every J: where a panel's own pass takes the segment path
+  // (seg_path, so the sums keep portfolio_multi's kernel and bits) with one chunk per row, and
+  // the nJ offset tables fit the LDS table; otherwise the per-J passes (the same partials)
+  const bool shared = seg_path(N, Kmax, n_bins) && lay.p.C == 1 &&
                       (legs ? nJ * Kmax * 4 : nJ * Kmax * (n_bins + 1)) <= SEG_MAXKD &&
                       cohort_nb_dispatch(n_bins, [&](auto nb) {
                         launch_cohort_js<decltype(nb)::value>(a, nJ, L, ws, false);
@@ -2387,7 +2396,7 @@ int csm_cohort_sums_js_grouped(csm_ctx* ctx, int32_t nJ, const int8_t* L, const 
                        Kmax, legs != 0, pan_plain(B, N)};
   const PfLayout& lay = a.lay;
   char* ws = (char*)workspace;
-  const bool shared = g_tune_cohort_seg && lay.seg && lay.p.C == 1 &&
+  const bool shared = seg_path(N, Kmax, n_bins) && lay.p.C == 1 &&
                       (legs ? nJ * Kmax * 4 : nJ * Kmax * (n_bins + 1)) <= SEG_MAXKD &&
                       cohort_nb_dispatch(n_bins, [&](auto nb) {
                         launch_cohort_js<decltype(nb)::value>(a, nJ, &L, &ws, true);
@@ -2420,8 +2429,7 @@ int csm_cohort_sums_legs(csm_ctx* ctx, const int8_t* L, const double* NR, const 
 // 0, the segment path -- launch_cohort's and launch_cohort_js's choice), so the workspace holds
 // the leg bitplanes.  (Tune knobs are set before a workspace is sized, csmom.h.)
 static bool legs_masks(const PfLayout& lay, bool legs, int64_t N, int Kmax, int n_bins) {
-  return g_tune_turn_mask && legs && (N & 3) == 0 && lay.seg && g_tune_cohort_seg &&
-         (int64_t)Kmax * (n_bins + 1) <= SEG_MAXKD &&
+  return g_tune_turn_mask && legs && (N & 3) == 0 && seg_path(N, Kmax, n_bins) &&
          (lay.p.Ct == 1 || lay.p.CHt % 256 == 0);
 }
 
