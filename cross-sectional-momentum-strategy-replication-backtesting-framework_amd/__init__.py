@@ -19,6 +19,8 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.run_signal                     momentum from every day row (rules D1..D6; beyond the reference)
   Engine.market_factor / market_model   equal-weight market, beta, idiosyncratic volatility and
   Engine.next_ret                       residual momentum; the next return of any signal (B1..B6)
+  Engine.daily_market / daily_sums      equal-weight daily market; daily beta, idiosyncratic and total
+  Engine.daily_model / daily_signals    volatility, skewness and MAX from daily returns (rules V1..V6)
   Engine.xs_regress / newey_west        per-month cross-sectional regressions (OLS, WLS, ridge) and
   Engine.fama_macbeth / fama_macbeth    Newey-West t-statistics of any monthly series (R1..R6)
   Engine.deciles_within / group_stats   qcut inside groups (sector-neutral deciles, dependent sorts)
@@ -34,7 +36,7 @@ a Python identifier).  Public API (reference file:line it replaces):
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyOut, Engine, FamaMacBethOut, GroupStatsOut, ICDecayOut, MarketModelOut,
+from .engine import (DailyModelOut, DailyOut, DailySums, Engine, FamaMacBethOut, GroupStatsOut, ICDecayOut, MarketModelOut,
                      MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RankICOut, SignalsOut,
                      XsRegressOut, absent_tensor, is_absent, quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
@@ -59,7 +61,7 @@ __all__ = [
     "compute_monthly_momentum_from_daily", "compute_monthly_turnover", "get_engine",
     "DensePanel", "from_long", "month_offsets", "monthly_frame", "ReplicationResult",
     "assign_deciles_per_date", "monthly_replication", "ensure_dir", "save_plot", "sharpe",
-    "DailyOut", "daily_portfolio_returns", "MonthStats", "SignalsOut",
+    "DailyOut", "daily_portfolio_returns", "MonthStats", "SignalsOut", "DailySums", "DailyModelOut",
     "MarketModelOut", "XsRegressOut", "NeweyWestOut", "FamaMacBethOut", "FamaMacBethResult",
     "fama_macbeth", "GroupStatsOut", "DependentSortResult", "dependent_double_sort",
     "NeutralResult", "group_ids", "neutral_momentum",

@@ -99,6 +99,12 @@ SIGNATURES = {
     "csm_market_model": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _i32, _i32, _i32, _i32, _p, _p,
                                         _p, _p, _p]),
     "csm_next_ret": (ctypes.c_int, [_p, _p, _p, _i32, _i64, _p]),
+    "csm_daily_market_workspace": (ctypes.c_int64, [_i64, _i64]),
+    "csm_daily_market": (ctypes.c_int, [_p, _p, _i64, _i64, _i32, _i32, _p, _p, _p]),
+    "csm_daily_sums": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i32, _i32, _i32, _p, _p, _p,
+                                      _p, _p, _p, _p, _p]),
+    "csm_daily_model": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32,
+                                       _p, _p, _p, _p, _p, _p]),
     "csm_xs_regress": (ctypes.c_int, [_p, _p, _p, _i32, _p, _i32, _i64, _i32, _f64, _i32, _p, _p,
                                       _p]),
     "csm_newey_west": (ctypes.c_int, [_p, _p, _i32, _i32, _i64, _i32, _p, _p, _p, _p]),

@@ -17,10 +17,9 @@
 //                     oldest first every month, and the next return of each requested signal by
 //                     scan.h's rank_step / pending_finish on a (psff, prev) pair of its own.
 #include "csm_common.h"
+#include "daytrip.h"
 #include "scan.h"
 
-#define MS_THREADS 256
-#define MS_TRIP 8        // day rows per trip: two trips of two assets are 64 VGPRs of buffers
 #define WS_THREADS 64
 #define WS_MAXJ 36
 
@@ -65,41 +64,6 @@ __device__ __forceinline__ void ms_step(MsAcc& s, double x) {
   s.hi = (ok && !(x <= s.hi)) ? x : s.hi;   // (NaN hi: the first priced row)
   s.p1 = have ? s.p1 : (ok ? x : s.p1);
   s.last = ok ? x : s.last;
-}
-
-__device__ __forceinline__ int64_t ms_clip(int64_t d, int64_t lo, int64_t hi) {
-  return d < lo ? lo : (d > hi ? hi : d);
-}
-
-// Rows [d, d + MS_TRIP) of the lane's assets; rows from dB on are ABSENT placeholders, which
-// change nothing.
-template <int VEC>
-__device__ __forceinline__ void ms_load(double (&x)[MS_TRIP][VEC], const double* __restrict__ P,
-                                        int64_t N, int64_t a, int64_t d, int64_t dB) {
-  const double* p = P + d * N + a;
-  auto row = [&](int i) {
-    if (VEC == 2) {
-      const double2 t = *reinterpret_cast<const double2*>(p + (int64_t)i * N);
-      x[i][0] = t.x;
-      x[i][VEC - 1] = t.y;
-    } else {
-      x[i][0] = p[(int64_t)i * N];
-    }
-  };
-  if (d + MS_TRIP <= dB) {   // (uniform) a whole trip: no predicate on any load
-#pragma unroll
-    for (int i = 0; i < MS_TRIP; ++i) row(i);
-  } else {
-#pragma unroll
-    for (int i = 0; i < MS_TRIP; ++i) {
-      if (d + i < dB) {
-        row(i);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) x[i][k] = absent_val();
-      }
-    }
-  }
 }
 
 template <int VEC>
@@ -308,8 +272,6 @@ __global__ __launch_bounds__(WS_THREADS) void k_window_signals(
   if (NRH && prev_h >= 0) NRH[(int64_t)prev_h * N + a] = pending_finish(absent_val(), psff_h);
   if (NRM && prev_m >= 0) NRM[(int64_t)prev_m * N + a] = pending_finish(absent_val(), psff_m);
 }
-
-static inline bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
 
 extern "C" {
 

@@ -136,6 +136,30 @@ class MarketModelOut:
     F: torch.Tensor | None = None        # [T_m] the factor regressed on (MKT when none was given)
 
 
+class DailySums(NamedTuple):
+    """csm_daily_sums (rule V3), each [T_m][N]: a month's raw moment sums over the days where the
+    asset's daily return r and the factor f both exist; daily_model's input."""
+    NO: torch.Tensor                     # int32, the observations
+    SR: torch.Tensor                     # sum of r
+    SF: torch.Tensor                     # sum of f
+    SRR: torch.Tensor                    # sum of r * r
+    SFF: torch.Tensor                    # sum of f * f
+    SRF: torch.Tensor                    # sum of r * f
+    SR3: torch.Tensor | None = None      # sum of (r * r) * r
+    RMAX: torch.Tensor | None = None     # the largest r (NaN = no observation)
+
+
+@dataclass
+class DailyModelOut:
+    """csm_daily_model (rule V4), each [T_m][N]; None = not asked for."""
+    DBETA: torch.Tensor | None = None    # slope of the daily returns on the factor
+    DIVOL: torch.Tensor | None = None    # residual standard deviation, n - 2 degrees of freedom
+    DTVOL: torch.Tensor | None = None    # standard deviation of the daily returns, n - 1
+    DSKEW: torch.Tensor | None = None    # their skewness (population moments)
+    DMAX: torch.Tensor | None = None     # the window's largest daily return
+    NOBS: torch.Tensor | None = None     # int32, observations in the window
+
+
 @dataclass
 class XsRegressOut:
     """csm_xs_regress (rules R1..R5): one cross-sectional regression per month."""
@@ -963,6 +987,69 @@ class Engine:
         self._call("csm_next_ret", _ptr(PM), _ptr(S), T_m, N, _ptr(NR))
         return NR
 
+    def daily_market(self, P, max_gap=10, min_assets=1, workspace=None):
+        """csm_daily_market (rules V1, V2): the equal-weight market return MKTD [T_d] of the daily
+        returns (a return reaches back over at most max_gap rows without a price) and NMD [T_d]
+        (int32), the assets behind each.  Returns (MKTD, NMD)."""
+        T_d, N = P.shape
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        MKTD = self.empty((T_d,))
+        NMD = self.empty((T_d,), torch.int32)
+        nbytes = int(self.lib.csm_daily_market_workspace(T_d, N))
+        if workspace is None or workspace.numel() * workspace.element_size() < nbytes:
+            workspace = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=self.device)
+        self._call("csm_daily_market", _ptr(P), T_d, N, int(max_gap), int(min_assets), _ptr(MKTD),
+                   _ptr(NMD), _ptr(workspace))
+        return MKTD, NMD
+
+    def daily_sums(self, P, month_start, FD, max_gap=10, max_month_days=None,
+                   with_sr3=True, with_rmax=True) -> DailySums:
+        """csm_daily_sums (rule V3): one pass over P for each (month, asset)'s raw moment sums of
+        its daily returns and the factor FD [T_d] (daily_market's MKTD, or any series)."""
+        T_d, N = P.shape
+        T_m = month_start.numel() - 1
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        _need(FD, "FD", torch.float64, (T_d,), self.device)
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        NO = self.empty((T_m, N), torch.int32)
+        SR, SF, SRR, SFF, SRF = (self.empty((T_m, N)) for _ in range(5))
+        SR3 = self.empty((T_m, N)) if with_sr3 else None
+        RMAX = self.empty((T_m, N)) if with_rmax else None
+        self._call("csm_daily_sums", _ptr(P), _ptr(FD), T_d, N, _ptr(month_start), T_m,
+                   int(max_month_days), int(max_gap), _ptr(NO), _ptr(SR), _ptr(SF), _ptr(SRR),
+                   _ptr(SFF), _ptr(SRF), _ptr(SR3), _ptr(RMAX))
+        return DailySums(NO, SR, SF, SRR, SFF, SRF, SR3, RMAX)
+
+    DAILY_OUTPUTS = ("DBETA", "DIVOL", "DTVOL", "DSKEW", "DMAX", "NOBS")
+
+    def daily_model(self, sums: DailySums, window=1, min_obs=None, outputs=None) -> DailyModelOut:
+        """csm_daily_model (rule V4) on daily_sums' panels over `window` calendar months (1..12):
+        the daily beta DBETA, idiosyncratic volatility DIVOL, total volatility DTVOL, skewness
+        DSKEW, the largest daily return DMAX and NOBS.  min_obs counts days (default 15 * window).
+        outputs: the DailyModelOut fields to compute (default: all the sums given allow)."""
+        T_m, N = sums.SR.shape
+        _need(sums.NO, "NO", torch.int32, (T_m, N), self.device)
+        for k in ("SR", "SF", "SRR", "SFF", "SRF", "SR3", "RMAX"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.float64, (T_m, N), self.device)
+        if outputs is None:
+            outputs = tuple(k for k in self.DAILY_OUTPUTS
+                            if not (k == "DSKEW" and sums.SR3 is None)
+                            and not (k == "DMAX" and sums.RMAX is None))
+        unknown = set(outputs) - set(self.DAILY_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = 15 * window if min_obs is None else int(min_obs)
+        o = {k: self.empty((T_m, N), torch.int32 if k == "NOBS" else torch.float64)
+             for k in outputs}
+        self._call("csm_daily_model", *(_ptr(t) for t in sums), T_m, N, window, min_obs,
+                   *(_ptr(o.get(k)) for k in self.DAILY_OUTPUTS))
+        return DailyModelOut(**o)
+
     def xs_regress(self, Y, signals, W=None, standardize=False, ridge=0.0,
                    min_obs=None) -> XsRegressOut:
         """csm_xs_regress (rules R1..R5): each month's regression of Y [T_m][N] on the K signals
@@ -1600,7 +1687,27 @@ class Engine:
         return PipelineOut(PM=PM, M=M, NR=NR, L=L, EW=EW, CNT=CNT, LS=LS, R=R, VOL=VOL, NV=NV)
 
     MARKET_SIGNALS = {"resid_mom": "RESMOM", "beta": "BETA", "ivol": "IVOL"}
-    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS)
+    DAILY_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL", "dskew": "DSKEW", "max": "DMAX"}
+    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS)
+
+    def daily_signals(self, P, month_start, names, window=None, min_obs=None, max_gap=10):
+        """{name: [T_m][N]} for names of DAILY_SIGNALS (rules V1..V4): the daily market, one pass
+        for the month sums on it, and one model call per window.  window None: 12 months for
+        "dbeta", 1 for the others; min_obs counts days (default 15 * window)."""
+        MKTD, _ = self.daily_market(P, max_gap)
+        sums = self.daily_sums(P, month_start, MKTD, max_gap, with_sr3="dskew" in names,
+                               with_rmax="max" in names)
+        by_window = {}
+        for n in names:
+            w = (12 if n == "dbeta" else 1) if window is None else int(window)
+            by_window.setdefault(w, []).append(n)
+        out = {}
+        for w, group in by_window.items():
+            dm = self.daily_model(sums, w, min_obs,
+                                  outputs=tuple(self.DAILY_SIGNALS[n] for n in group))
+            for n in group:
+                out[n] = getattr(dm, self.DAILY_SIGNALS[n])
+        return out
 
     def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
                    min_obs=None) -> PipelineOut:
@@ -1612,11 +1719,19 @@ class Engine:
         asset's month returns on the equal-weight market over `window` months: "resid_mom", the
         residual momentum of the J months that end `skip` months back, "beta" or "ivol".  For
         these three a `window` left at its default of 12 means 36, and min_obs counts months
-        (default max(2, ceil(2 * window / 3)))."""
+        (default max(2, ceil(2 * window / 3))).
+        Or on a signal of the daily returns against the equal-weight daily market (rules
+        V1..V6): "dbeta", "divol", "dskew" or "max".  For these a `window` left at its default
+        means 12 months for "dbeta" and 1 month for the other three, and min_obs counts days
+        (default 15 * window)."""
         if signal not in self.RUN_SIGNALS:
             raise ValueError(f"signal must be one of {self.RUN_SIGNALS}, got {signal!r}")
         st = self.month_stats(P, month_start)
-        if signal in self.MARKET_SIGNALS:
+        if signal in self.DAILY_SIGNALS:
+            S = self.daily_signals(P, month_start, (signal,), None if window == 12 else window,
+                                   min_obs)[signal]
+            NR = self.next_ret(st.PM, S)
+        elif signal in self.MARKET_SIGNALS:
             field = self.MARKET_SIGNALS[signal]
             mm = self.market_model(st.PM, window=36 if window == 12 else window, J=J, skip=skip,
                                    min_obs=min_obs, outputs=(field,))

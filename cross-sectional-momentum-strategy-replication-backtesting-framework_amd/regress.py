@@ -30,8 +30,8 @@ class FamaMacBethResult:
 def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None):
     """The named signals of a daily panel on the device, each [T_m][N], with the B1 month return
     X: "mom" (mom_J), "rev" (the month's own return) and Engine.RUN_SIGNALS' names, built by the
-    calls run_signal makes.  window None: 12 months for the daily signals, 36 for the market
-    model's."""
+    calls run_signal makes.  window None: 12 months for "high52" / "mom_vol" and "dbeta", 36 for
+    the monthly market model's, 1 for "divol", "dskew" and "max"."""
     unknown = [n for n in names if n not in SIGNAL_NAMES]
     if unknown:
         raise ValueError(f"signals must be among {SIGNAL_NAMES}, got {unknown}")
@@ -57,6 +57,9 @@ def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None)
                               outputs=tuple(Engine.MARKET_SIGNALS[n] for n in market))
         for n in market:
             out[n] = getattr(mm, Engine.MARKET_SIGNALS[n])
+    dsig = [n for n in names if n in Engine.DAILY_SIGNALS]
+    if dsig:
+        out.update(eng.daily_signals(P, month_start, dsig, window))
     return [out[n] for n in names], X
 
 

@@ -82,7 +82,9 @@ int csm_abi_version(void);
  * csm_signal_chunked workgroup makes before it gives up a wait, default 2^21; 0 gives up at
  * once, which only the tests of the CSM_E_TIMEOUT report set), "stats_chunks" (csm_month_stats's
  * month chunks: 0 auto, one month each | n >= 1 that many, clamped to T_m), "mm_chunks"
- * (csm_market_model's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits).
+ * (csm_market_model's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits),
+ * "dmkt_chunk_days" / "dsums_chunks" / "dmodel_chunks" (csm_daily_market's day rows per
+ * workgroup, csm_daily_sums's and csm_daily_model's month chunks: 0 auto; the same bits).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -707,6 +709,77 @@ int csm_market_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_
                      double* ALPHA, double* IVOL, double* RESMOM, int32_t* NOBS);
 int csm_next_ret(csm_ctx* ctx, const double* PM, const double* S, int32_t T_m, int64_t N,
                  double* NR);
+
+/*
+ * Signals of the daily returns against a daily market (rules V1..V6 in DESIGN.md section 7; no
+ * reference counterpart): the equal-weight daily market, and from each asset's daily market model
+ * the daily beta (Frazzini and Pedersen 2014), idiosyncratic volatility (Ang, Hodrick, Xing and
+ * Zhang 2006), total volatility, skewness and MAX, the largest daily return (Bali, Cakici and
+ * Whitelaw 2011).  Not csm_market_model's BETA / IVOL, which come from monthly returns.  A row is
+ * priced when P[d][a] is not NaN (the ABSENT payload counts as NaN).  fp64 throughout, every sum
+ * sequential in the stated order from 0.0, so two calls, and every launch shape, give the same
+ * bits.
+ *
+ * The daily return (V1): with d' the latest priced row before d, r[d][a] = P[d][a] / P[d'][a] - 1
+ * iff P[d][a] is priced, d' exists and d - d' <= max_gap (panel rows, ABSENT rows included); else
+ * there is no observation.  max_gap in [1, 32].  Never month-bounded: a month's first priced day
+ * takes its return from the previous month's rows.  On a panel with every cell priced r is
+ * pandas' pct_change bit for bit.
+ *
+ * csm_daily_market (V2), all T_d rows:
+ *   NMD  [T_d] int32 nullable out: the assets with an observation on day d
+ *   MKTD [T_d] out: (sum of r[d] over those assets) / NMD[d] when NMD[d] >= min_assets (>= 1),
+ *        else NaN.  The sum is csm_market_factor's: slices of 2048 assets, a lane's assets 256
+ *        apart in order, a 64-wide halving tree, the four waves, then the slices -- a function of
+ *        N alone.  |MKTD - exact| <= 2^-53 * (sum |r| + |MKTD|).
+ *   workspace: device buffer of csm_daily_market_workspace(T_d, N) bytes (0 for arguments the
+ *        call refuses), 8-B aligned, the caller's; T_d <= 2^31 - 1
+ *   "dmkt_chunk_days" (csm_tune: 0 auto | n >= 1 day rows per workgroup) only changes how many
+ *   workgroups there are.
+ *
+ * csm_daily_sums (V3): per (month t, asset), over the days d of [month_start[t], month_start[t+1])
+ * where r[d][a] and f = FD[d] are both not NaN, in day order from 0:
+ *   NO += 1, SR += r, SF += f, SRR += r * r, SFF += f * f, SRF += r * f, SR3 += (r * r) * r,
+ *   RMAX = the largest r (NaN if none).  A month without a day gives zeros and a NaN RMAX.
+ *   FD [T_d] on the device: MKTD, or any series of the caller's
+ *   NO [T_m][N] int32 out; SR, SF, SRR, SFF, SRF [T_m][N] out; SR3, RMAX [T_m][N] nullable out
+ *   max_month_days in [1, 32], csm_month_stats's bound
+ * Any N >= 1; even N with 16-B aligned P and outputs (8-B NO) takes two assets per lane, the same
+ * bits.  "dsums_chunks" (csm_tune: 0 auto | n >= 1 month chunks, clamped to T_m)
+ * only changes how many workgroups there are.  No row before month_start[0] - max_gap (clipped to
+ * 0) and none at or past month_start[T_m] is read.
+ *
+ * csm_daily_model (V4) over the Wm calendar months j = t-Wm+1 .. t (t-Wm+1 >= 0): each V3 sum
+ * added over j oldest first from 0.0, n the summed NO, nf = (double)n, one rounding per operation:
+ *   mr = SR / nf, mf = SF / nf, cff = SFF - SF * mf, crf = SRF - SR * mf, crr = SRR - SR * mr
+ *   DBETA = crf / cff: defined iff n >= min_obs and cff > 0
+ *   DIVOL = sqrt(max(q, 0) / (nf - 2)), q = crr - DBETA * crf: defined iff DBETA is and n >= 3
+ *   DTVOL = sqrt(crr / (nf - 1)): defined iff n >= min_obs, n >= 2 and crr >= 0
+ *   DSKEW = m3 / (v * sqrt(v)), v = crr / nf,
+ *           m3 = (SR3 - (3 * mr) * SRR + ((2 * SR) * mr) * mr) / nf: defined iff n >= min_obs,
+ *           n >= 3 and v > 0
+ *   DMAX  = the largest non-NaN RMAX[j] of the window: defined iff n >= min_obs
+ *   NOBS  = n (int32; 0 before the first whole window)
+ *   1 <= Wm <= 12;  min_obs >= 2 (days);  T_m >= 1;  any N >= 1
+ *   DBETA, DIVOL, DTVOL, DSKEW, DMAX [T_m][N] out, NOBS [T_m][N] int32 out: NaN where not
+ *       defined; every one nullable, at least one given; DSKEW needs SR3 and DMAX needs RMAX
+ *       (nullable inputs otherwise)
+ * "dmodel_chunks" (csm_tune: 0 auto, one month per chunk | n >= 1 that many, clamped to T_m) only
+ * changes how many workgroups there are; only the sums a requested output depends on are read.  The next return of any of these signals is csm_next_ret's.
+ * +-inf and zero or negative prices are out of contract.
+ */
+int64_t csm_daily_market_workspace(int64_t T_d, int64_t N);
+int csm_daily_market(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N, int32_t max_gap,
+                     int32_t min_assets, double* MKTD, int32_t* NMD, void* workspace);
+int csm_daily_sums(csm_ctx* ctx, const double* P, const double* FD, int64_t T_d, int64_t N,
+                   const int64_t* month_start, int32_t T_m, int32_t max_month_days,
+                   int32_t max_gap, int32_t* NO, double* SR, double* SF, double* SRR, double* SFF,
+                   double* SRF, double* SR3, double* RMAX);
+int csm_daily_model(csm_ctx* ctx, const int32_t* NO, const double* SR, const double* SF,
+                    const double* SRR, const double* SFF, const double* SRF, const double* SR3,
+                    const double* RMAX, int32_t T_m, int64_t N, int32_t Wm, int32_t min_obs,
+                    double* DBETA, double* DIVOL, double* DTVOL, double* DSKEW, double* DMAX,
+                    int32_t* NOBS);
 
 /*
  * Fama-MacBeth (1973) cross-sectional regressions (rules R1..R6 in DESIGN.md section 7; the
