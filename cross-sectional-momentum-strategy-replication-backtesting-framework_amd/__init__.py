@@ -31,12 +31,15 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.deciles_bp / breakpoints       qcut edges from a subset of each date (NYSE breakpoints) applied
   Engine.screen / run_universe          to every cell, the edges themselves, price and size screens
   universe_momentum                     (rules U1..U6)
+  Engine.factor_model / daily_fsums     KF-factor rolling models, KF = 1..4: FF3-style betas, alphas,
+  Engine.daily_fmodel / lagged          idiosyncratic volatility, residual momentum, Dimson betas
+  residual_momentum / align_factors     (rules MF1..MF8)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyModelOut, DailyOut, DailySums, Engine, FamaMacBethOut, GroupStatsOut, ICDecayOut, MarketModelOut,
+from .engine import (DailyFModelOut, DailyFSums, DailyModelOut, DailyOut, DailySums, Engine, FactorModelOut, FamaMacBethOut, GroupStatsOut, ICDecayOut, MarketModelOut,
                      MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RankICOut, SignalsOut,
                      XsRegressOut, absent_tensor, is_absent, quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
@@ -45,6 +48,7 @@ from .lesw import (DependentSortResult, DoubleSortResult, dependent_double_sort,
                    momentum_volume_double_sort)
 from .neutral import NeutralResult, group_ids, neutral_momentum
 from .universe import UniverseResult, breakpoint_mask, shares_row, universe_momentum
+from .factors import ResidualMomentumResult, align_factors, residual_momentum
 from .regress import FamaMacBethResult, fama_macbeth
 from .ic import ICResult, information_coefficient
 from .panel import DensePanel, from_long, month_offsets, monthly_frame
@@ -67,4 +71,6 @@ __all__ = [
     "NeutralResult", "group_ids", "neutral_momentum",
     "RankICOut", "ICDecayOut", "ICResult", "information_coefficient",
     "UniverseResult", "breakpoint_mask", "shares_row", "universe_momentum",
+    "FactorModelOut", "DailyFSums", "DailyFModelOut", "ResidualMomentumResult", "align_factors",
+    "residual_momentum",
 ]

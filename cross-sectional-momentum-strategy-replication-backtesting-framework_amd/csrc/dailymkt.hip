@@ -20,6 +20,12 @@
 //                     lane) x (chunk of consecutive months), the same lead-in, FD[d] a uniform
 //                     load, a month's sums flushed as the walk passes its end.  No barrier, no LDS,
 //                     no state in memory (csm_tune "dsums_chunks").
+//   k_daily_fsums     MF6.  k_daily_sums's walk on KF factors (a template on KF = 1..4): a day
+//                     row's KF factor values and their pair products are uniform, computed once
+//                     per row; two assets per lane up to DF_PAIR_MAXKF factors, one past it
+//                     (csm_tune "dfsums_chunks").
+//   k_daily_fmodel    MF7.  k_daily_model's shape on the MF6 panels; fsolve.h solves each
+//                     window's normal equations (csm_tune "dfmodel_chunks").
 //   k_daily_model     V4.  A lane per asset over (64 assets) x (chunk of consecutive months); every
 //                     window's sums are added again from its oldest month, read from the V3 panels
 //                     (a window is at most 12 months and its rows are L2 hits after the first
@@ -28,6 +34,7 @@
 //                     there are.
 #include "csm_common.h"
 #include "daytrip.h"
+#include "fsolve.h"
 #include "scan.h"
 
 #define DM_THREADS 256
@@ -38,18 +45,34 @@
 #define DM_MAXGAP 32
 #define DMD_THREADS 64
 #define DMD_MAXW 12
+// k_daily_fsums: the largest KF that takes two assets per lane and loads its factor rows a trip
+// ahead, as k_daily_sums does.  Past it the 3 + 2 KF + KF (KF + 1) / 2 accumulators per asset, twice
+// over, and two trips of KF factor rows fill the 256 VGPRs and leave a SIMD one wave, so a lane
+// takes one asset and a trip loads its own factor rows.  MI355X, 100,000 x 10,000 days / 5,000 x
+// 6,522 days, ms (profiles/r15/bench_fsums_*.log; k_daily_sums on six panels 2.19 / 0.120):
+//   KF  paired, ahead   paired, own rows   one per lane, ahead   one per lane, own rows
+//   1   2.15 / 0.110    --                 2.28 / 0.110          --
+//   2   2.86 / 0.136    --                 3.15 / 0.122          --
+//   3   6.20 / 0.275    4.95 / 0.232       4.24 / 0.168          3.91 / 0.158
+//   4   8.18 / 0.331    7.12 / 0.286       6.47 / 0.254          5.10 / 0.211
+#define DF_PAIR_MAXKF 2
 
 // "dmkt_chunk_days": day rows per chunk of k_daily_market, 0 auto (dm_auto_chunk_days) | n >= 1
 // "dsums_chunks":    month chunks of k_daily_sums, 0 auto (ds_auto_chunks) | n >= 1 that many
 // "dmodel_chunks":   month chunks of k_daily_model, 0 auto, one month per chunk | n >= 1 that many
 // (both clamped to T_m).  Every value gives the same bits.
+// "dfsums_chunks" / "dfmodel_chunks": the same two for k_daily_fsums and k_daily_fmodel.
 static int g_tune_dmkt_chunk_days = 0;
 static int g_tune_dsums_chunks = 0;
 static int g_tune_dmodel_chunks = 0;
+static int g_tune_dfsums_chunks = 0;
+static int g_tune_dfmodel_chunks = 0;
 static const TuneKnob g_knobs[] = {
     {"dmkt_chunk_days", &g_tune_dmkt_chunk_days, [](int v) { return v >= 0; }},
     {"dsums_chunks", &g_tune_dsums_chunks, [](int v) { return v >= 0; }},
     {"dmodel_chunks", &g_tune_dmodel_chunks, [](int v) { return v >= 0; }},
+    {"dfsums_chunks", &g_tune_dfsums_chunks, [](int v) { return v >= 0; }},
+    {"dfmodel_chunks", &g_tune_dfmodel_chunks, [](int v) { return v >= 0; }},
 };
 
 // ------------------------------------------------------------------------------- V1
@@ -340,6 +363,211 @@ static inline int ds_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
   return (int)G;
 }
 
+// ------------------------------------------------------------------------------- MF6
+// One asset's sums of the month being walked, on KF factors.
+template <int KF>
+struct DfAcc {
+  double sr, srr, sf[KF], srf[KF], sff[KF * (KF + 1) / 2];
+  int no;
+};
+
+template <int KF>
+__device__ __forceinline__ void df_reset(DfAcc<KF>& s) {
+  s.sr = s.srr = 0.0;
+#pragma unroll
+  for (int c = 0; c < KF; ++c) s.sf[c] = s.srf[c] = 0.0;
+#pragma unroll
+  for (int p = 0; p < fs_pairs(KF); ++p) s.sff[p] = 0.0;
+  s.no = 0;
+}
+
+// One day row's factor values, whether all KF are there, and their pair products: the same for
+// every asset, so computed once per row.
+template <int KF>
+struct DfRow {
+  double f[KF], ff[KF * (KF + 1) / 2];
+  bool ok;
+};
+
+template <int KF>
+__device__ __forceinline__ DfRow<KF> df_row(const double (&f)[KF]) {
+  DfRow<KF> w;
+  w.ok = true;
+#pragma unroll
+  for (int c = 0; c < KF; ++c) {
+    w.f[c] = f[c];
+    w.ok = w.ok && !isnan_d(f[c]);
+  }
+#pragma unroll
+  for (int c = 0; c < KF; ++c) {
+#pragma unroll
+    for (int e = c; e < KF; ++e) w.ff[fs_pair(KF, c, e)] = f[c] * f[e];
+  }
+  return w;
+}
+
+// One day row of one asset: the V1 state moves whatever the factor row is; the sums take the row
+// iff r is not NaN and the day has a factor row.
+template <int KF>
+__device__ __forceinline__ void df_step(DfAcc<KF>& s, DrLane& l, double x, const DfRow<KF>& w,
+                                        int max_gap) {
+  const double r = dr_step(l, x, max_gap);
+  const bool obs = !isnan_d(r) && w.ok;
+  s.no += obs ? 1 : 0;
+  s.sr = obs ? s.sr + r : s.sr;
+  s.srr = obs ? s.srr + r * r : s.srr;
+#pragma unroll
+  for (int c = 0; c < KF; ++c) {
+    s.sf[c] = obs ? s.sf[c] + w.f[c] : s.sf[c];
+    s.srf[c] = obs ? s.srf[c] + r * w.f[c] : s.srf[c];
+  }
+#pragma unroll
+  for (int p = 0; p < fs_pairs(KF); ++p) s.sff[p] = obs ? s.sff[p] + w.ff[p] : s.sff[p];
+}
+
+struct DfOut {
+  int32_t* NO;
+  double *SR, *SRR;   // [T_m][N]
+  double *SF, *SRF;   // [KF][T_m][N]
+  double* SFF;        // [KF (KF + 1) / 2][T_m][N]
+};
+
+template <int VEC>
+__device__ __forceinline__ void df_store(double* p, double lo, double hi) {
+  if (VEC == 2)
+    store_pair(p, lo, hi);
+  else
+    p[0] = lo;
+}
+
+// o: the (month, asset) cell; plane: T_m * N, the stride between a panel's factor planes.
+template <int KF, int VEC>
+__device__ __forceinline__ void df_flush(const DfAcc<KF> (&s)[VEC], int64_t o, int64_t plane,
+                                         const DfOut& out) {
+  if (VEC == 2)
+    *reinterpret_cast<int2*>(out.NO + o) = make_int2(s[0].no, s[VEC - 1].no);
+  else
+    out.NO[o] = s[0].no;
+  df_store<VEC>(out.SR + o, s[0].sr, s[VEC - 1].sr);
+  df_store<VEC>(out.SRR + o, s[0].srr, s[VEC - 1].srr);
+#pragma unroll
+  for (int c = 0; c < KF; ++c) {
+    df_store<VEC>(out.SF + c * plane + o, s[0].sf[c], s[VEC - 1].sf[c]);
+    df_store<VEC>(out.SRF + c * plane + o, s[0].srf[c], s[VEC - 1].srf[c]);
+  }
+#pragma unroll
+  for (int p = 0; p < fs_pairs(KF); ++p)
+    df_store<VEC>(out.SFF + p * plane + o, s[0].sff[p], s[VEC - 1].sff[p]);
+}
+
+// FD[d .. d + MS_TRIP)[KF] (uniform); NaN from dB on.
+template <int KF>
+__device__ __forceinline__ void df_fload(double (&f)[MS_TRIP][KF], const double* __restrict__ FD,
+                                         int64_t d, int64_t dB) {
+#pragma unroll
+  for (int i = 0; i < MS_TRIP; ++i) {
+#pragma unroll
+    for (int c = 0; c < KF; ++c) f[i][c] = d + i < dB ? FD[(d + i) * KF + c] : qnan();
+  }
+}
+
+// k_daily_sums's walk on KF factors.
+template <int KF, int VEC>
+__global__ __launch_bounds__(MS_THREADS) void k_daily_fsums(
+    const double* __restrict__ P, const double* __restrict__ FD, int64_t T_d, int64_t N,
+    const int64_t* __restrict__ ms, int T_m, int G, int max_gap, DfOut out) {
+  const int64_t a = ((int64_t)blockIdx.x * MS_THREADS + threadIdx.x) * VEC;
+  if (a >= N) return;   // (no barrier anywhere below)
+  int m0, m1;
+  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
+  const int64_t dA = ms_clip(ms[m0], 0, T_d), dB = ms_clip(ms[m1], dA, T_d);
+  const int64_t plane = (int64_t)T_m * N;
+  int m = m0;
+  int64_t nb = ms_clip(ms[m0 + 1], dA, dB);   // end of month m
+  DrLane lane[VEC];
+  dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
+  DfAcc<KF> acc[VEC];
+#pragma unroll
+  for (int k = 0; k < VEC; ++k) df_reset<KF>(acc[k]);
+  auto next_month = [&]() {   // (uniform) month m is complete; the V1 state runs on
+    df_flush<KF, VEC>(acc, (int64_t)m * N + a, plane, out);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) df_reset<KF>(acc[k]);
+    ++m;
+    nb = m < m1 ? ms_clip(ms[m + 1], dA, dB) : dB;
+  };
+  // the next trip's factor rows are loaded a trip ahead up to DF_PAIR_MAXKF factors; past it a
+  // trip loads its own rows
+  constexpr bool PF = KF <= DF_PAIR_MAXKF;
+  double cur[MS_TRIP][VEC], nxt[MS_TRIP][VEC], fc[MS_TRIP][KF], fn[MS_TRIP][KF];
+  ms_load<VEC>(cur, P, N, a, dA, dB);
+  if (PF) df_fload<KF>(fc, FD, dA, dB);
+  for (int64_t d = dA; d < dB; d += MS_TRIP) {
+    ms_load<VEC>(nxt, P, N, a, d + MS_TRIP, dB);
+    if (PF)
+      df_fload<KF>(fn, FD, d + MS_TRIP, dB);
+    else
+      df_fload<KF>(fc, FD, d, dB);
+    if (d + MS_TRIP <= nb) {   // (uniform) the trip lies inside month m: one straight block
+#pragma unroll
+      for (int i = 0; i < MS_TRIP; ++i) {
+        const DfRow<KF> w = df_row<KF>(fc[i]);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) df_step<KF>(acc[k], lane[k], cur[i][k], w, max_gap);
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < MS_TRIP; ++i) {
+        while (m < m1 && d + i >= nb) next_month();   // (zero-length months: several)
+        const DfRow<KF> w = df_row<KF>(fc[i]);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) df_step<KF>(acc[k], lane[k], cur[i][k], w, max_gap);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < MS_TRIP; ++i) {
+      if (PF) {
+#pragma unroll
+        for (int c = 0; c < KF; ++c) fc[i][c] = fn[i][c];
+      }
+#pragma unroll
+      for (int k = 0; k < VEC; ++k) cur[i][k] = nxt[i][k];
+    }
+  }
+  while (m < m1) next_month();   // the last month, and whatever zero-length months follow it
+}
+
+// Auto chunk count of k_daily_fsums: ds_auto_chunks' rule with about 32 (slice, chunk) workgroups
+// per CU in place of eight: the deeper accumulator set leaves a CU fewer resident waves, and more,
+// shorter chunks even the fill out.  MI355X (profiles/r15/bench_fsums_sweep.log), KF = 1 / KF = 4:
+// 100,000 assets x 461 months 3 / 6 / 12 / 30 / 100 chunks 2.65 / 2.14 / 2.06 / 1.97 / 2.16 ms and
+// 5.26 / 5.09 / 4.65 / 4.48 / 4.61 ms (auto 42 and 21: 2.21 and 4.57 ms in bench_factor.log,
+// k_daily_sums 2.43 there; eight per CU gave 11 and 6 chunks, 2.06 and 5.00 ms in the sweep's run);
+// 5,000 assets x 300 months 3 / 6 / 12 / 30 / 100 chunks 0.703 / 0.370 / 0.207 / 0.135 / 0.114 ms
+// and 1.023 / 0.532 / 0.288 / 0.259 / 0.216 ms (auto 100)
+static inline int df_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
+  const int64_t want = (int64_t)32 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
+  int64_t G = (want + slices - 1) / slices;
+  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
+  if (G > most) G = most;
+  return (int)G;
+}
+
+template <int KF>
+static inline void df_launch(csm_ctx* ctx, bool v2, dim3 grid, const double* P, const double* FD,
+                             int64_t T_d, int64_t N, const int64_t* ms, int T_m, int G,
+                             int max_gap, const DfOut& out) {
+  if constexpr (KF <= DF_PAIR_MAXKF) {
+    if (v2) {
+      hipLaunchKernelGGL((k_daily_fsums<KF, 2>), grid, dim3(MS_THREADS), 0, ctx->stream, P, FD,
+                         T_d, N, ms, T_m, G, max_gap, out);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((k_daily_fsums<KF, 1>), grid, dim3(MS_THREADS), 0, ctx->stream, P, FD, T_d,
+                     N, ms, T_m, G, max_gap, out);
+}
+
 // ------------------------------------------------------------------------------- V4
 struct DmdIn {
   const int32_t* NO;
@@ -413,6 +641,105 @@ __global__ __launch_bounds__(DMD_THREADS) void k_daily_model(DmdIn in, int T_m, 
     if (o.DMAX) o.DMAX[ot] = dmax;
     if (o.NOBS) o.NOBS[ot] = n;
   }
+}
+
+// ------------------------------------------------------------------------------- MF7
+struct DfmIn {
+  const int32_t* NO;
+  const double *SR, *SRR, *SF, *SRF, *SFF;
+};
+struct DfmOut {
+  double* DBETA;   // [KF][T_m][N]
+  double *DALPHA, *DIVOL, *DR2;
+  int32_t* NOBS;
+};
+
+// k_daily_model's shape on KF factors.
+template <int KF>
+__global__ __launch_bounds__(DMD_THREADS) void k_daily_fmodel(DfmIn in, int T_m, int64_t N, int Wm,
+                                                             int min_obs, int G, DfmOut o) {
+  constexpr int NP = fs_pairs(KF);
+  const int64_t a = (int64_t)blockIdx.x * DMD_THREADS + threadIdx.x;
+  if (a >= N) return;
+  int m0, m1;
+  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
+  const double NaN = qnan();
+  const int64_t plane = (int64_t)T_m * N;
+  // (uniform) the sums somebody reads: NOBS alone needs NO only
+  const bool needrr = o.DIVOL || o.DR2;                       // SRR
+  const bool needb = o.DBETA || o.DALPHA || needrr;           // SR, SF, SRF, SFF
+  for (int t = m0; t < m1; ++t) {
+    double beta[KF], alpha = NaN, ivol = NaN, r2 = NaN;
+#pragma unroll
+    for (int c = 0; c < KF; ++c) beta[c] = NaN;
+    int n = 0;
+    if (t - Wm + 1 >= 0) {   // (uniform) a whole window, added oldest month first
+      double sr = 0.0, srr = 0.0, sf[KF], srf[KF], sff[NP];
+#pragma unroll
+      for (int c = 0; c < KF; ++c) sf[c] = srf[c] = 0.0;
+#pragma unroll
+      for (int p = 0; p < NP; ++p) sff[p] = 0.0;
+#pragma unroll 2
+      for (int j = t - Wm + 1; j <= t; ++j) {
+        const int64_t oj = (int64_t)j * N + a;
+        n += in.NO[oj];
+        if (needrr) srr += in.SRR[oj];
+        if (needb) {
+          sr += in.SR[oj];
+#pragma unroll
+          for (int c = 0; c < KF; ++c) {
+            sf[c] += in.SF[c * plane + oj];
+            srf[c] += in.SRF[c * plane + oj];
+          }
+#pragma unroll
+          for (int p = 0; p < NP; ++p) sff[p] += in.SFF[p * plane + oj];
+        }
+      }
+      const double nf = (double)n;
+      const double mr = sr / nf;
+      double mf[KF], A[NP], b[KF], g[KF];
+#pragma unroll
+      for (int c = 0; c < KF; ++c) mf[c] = sf[c] / nf;
+#pragma unroll
+      for (int c = 0; c < KF; ++c) {
+#pragma unroll
+        for (int e = c; e < KF; ++e)
+          A[fs_pair(KF, c, e)] = sff[fs_pair(KF, c, e)] - sf[c] * mf[e];
+        b[c] = srf[c] - sr * mf[c];
+      }
+      const double crr = srr - sr * mr;
+      const bool solved = fs_solve<KF>(A, b, g);
+      if (n >= min_obs && solved) {
+        alpha = mr;
+        double q = crr;
+#pragma unroll
+        for (int c = 0; c < KF; ++c) {
+          beta[c] = g[c];
+          alpha = alpha - g[c] * mf[c];
+          q = q - g[c] * b[c];
+        }
+        q = q < 0.0 ? 0.0 : q;
+        if (n >= KF + 2) ivol = sqrt(q / (nf - (KF + 1.0)));
+        if (crr > 0.0) r2 = 1.0 - q / crr;
+      }
+    }
+    const int64_t ot = (int64_t)t * N + a;
+    if (o.DBETA) {
+#pragma unroll
+      for (int c = 0; c < KF; ++c) o.DBETA[c * plane + ot] = beta[c];
+    }
+    if (o.DALPHA) o.DALPHA[ot] = alpha;
+    if (o.DIVOL) o.DIVOL[ot] = ivol;
+    if (o.DR2) o.DR2[ot] = r2;
+    if (o.NOBS) o.NOBS[ot] = n;
+  }
+}
+
+template <int KF>
+static inline void dfm_launch(csm_ctx* ctx, dim3 grid, const DfmIn& in, int T_m, int64_t N, int Wm,
+                              int min_obs, int G, const DfmOut& o) {
+  hipLaunchKernelGGL(k_daily_fmodel<KF>, grid, dim3(DMD_THREADS), 0, ctx->stream, in, T_m, N, Wm,
+                     min_obs, G, o);
 }
 
 
@@ -522,6 +849,90 @@ int csm_daily_model(csm_ctx* ctx, const int32_t* NO, const double* SR, const dou
   hipLaunchKernelGGL(k_daily_model, dim3((unsigned)slices, (unsigned)G), dim3(DMD_THREADS), 0,
                      ctx->stream, in, T_m, N, Wm, min_obs, (int)G, o);
   LAUNCH_CHECK(ctx, "k_daily_model");
+  return CSM_OK;
+}
+
+int csm_daily_fsums(csm_ctx* ctx, const double* P, const double* FD, int64_t T_d, int64_t N,
+                    int32_t KF, const int64_t* month_start, int32_t T_m, int32_t max_month_days,
+                    int32_t max_gap, int32_t* NO, double* SR, double* SRR, double* SF, double* SRF,
+                    double* SFF) {
+  int r = prep(ctx);
+  if (r) return r;
+  if (!P || !FD || !month_start || !NO || !SR || !SRR || !SF || !SRF || !SFF || T_d < 1 ||
+      N < 1 || T_m < 1 || T_d > ((int64_t)1 << 40) / N)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fsums: bad arguments (T_d=%lld N=%lld T_m=%d)",
+                   (long long)T_d, (long long)N, T_m);
+  if (KF < 1 || KF > FS_MAXKF)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fsums: KF=%d is outside [1, %d]", KF, FS_MAXKF);
+  if ((int64_t)T_m * fs_pairs(KF) > ((int64_t)1 << 40) / N)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fsums: bad arguments (T_m=%d N=%lld KF=%d)", T_m,
+                   (long long)N, KF);
+  if (max_month_days < 1 || max_month_days > 32)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fsums: max_month_days=%d is outside [1, 32]",
+                   max_month_days);
+  if (max_gap < 1 || max_gap > DM_MAXGAP)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fsums: max_gap=%d is outside [1, %d]", max_gap,
+                   DM_MAXGAP);
+  const bool v2 = KF <= DF_PAIR_MAXKF && (N % 2 == 0) && aligned16(P) && aligned8(NO) &&
+                  aligned16(SR) && aligned16(SRR) && aligned16(SF) && aligned16(SRF) &&
+                  aligned16(SFF);
+  const int vec = v2 ? 2 : 1;
+  const int64_t slices = (N + (int64_t)MS_THREADS * vec - 1) / ((int64_t)MS_THREADS * vec);
+  int64_t G = g_tune_dfsums_chunks > 0 ? g_tune_dfsums_chunks : df_auto_chunks(ctx, slices, T_m);
+  if (G > T_m) G = T_m;
+  if (G > 65535) G = 65535;   // (grid.y)
+  const int g = (int)G;
+  const dim3 grid((unsigned)slices, (unsigned)g);
+  const DfOut out{NO, SR, SRR, SF, SRF, SFF};
+  switch (KF) {
+    case 1: df_launch<1>(ctx, v2, grid, P, FD, T_d, N, month_start, T_m, g, max_gap, out); break;
+    case 2: df_launch<2>(ctx, v2, grid, P, FD, T_d, N, month_start, T_m, g, max_gap, out); break;
+    case 3: df_launch<3>(ctx, v2, grid, P, FD, T_d, N, month_start, T_m, g, max_gap, out); break;
+    default: df_launch<4>(ctx, v2, grid, P, FD, T_d, N, month_start, T_m, g, max_gap, out); break;
+  }
+  LAUNCH_CHECK(ctx, "k_daily_fsums");
+  return CSM_OK;
+}
+
+int csm_daily_fmodel(csm_ctx* ctx, const int32_t* NO, const double* SR, const double* SRR,
+                     const double* SF, const double* SRF, const double* SFF, int32_t T_m,
+                     int64_t N, int32_t KF, int32_t Wm, int32_t min_obs, double* DBETA,
+                     double* DALPHA, double* DIVOL, double* DR2, int32_t* NOBS) {
+  int r = prep(ctx);
+  if (r) return r;
+  if (!NO || !SR || !SRR || !SF || !SRF || !SFF || bad_panel(T_m, N))
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fmodel: bad arguments (T_m=%d N=%lld)", T_m,
+                   (long long)N);
+  if (KF < 1 || KF > FS_MAXKF)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fmodel: KF=%d is outside [1, %d]", KF, FS_MAXKF);
+  if ((int64_t)T_m * fs_pairs(KF) > ((int64_t)1 << 40) / N)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fmodel: bad arguments (T_m=%d N=%lld KF=%d)", T_m,
+                   (long long)N, KF);
+  if (!DBETA && !DALPHA && !DIVOL && !DR2 && !NOBS)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fmodel: no output requested");
+  if (Wm < 1 || Wm > DMD_MAXW)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fmodel: Wm=%d is outside [1, %d]", Wm, DMD_MAXW);
+  if (min_obs < KF + 1)
+    return set_err(ctx, CSM_E_INVAL, "csm_daily_fmodel: min_obs=%d must be at least KF+1=%d",
+                   min_obs, KF + 1);
+  const int64_t slices = (N + DMD_THREADS - 1) / DMD_THREADS;
+  // auto is one month per chunk, csm_daily_model's rule: a chunk needs no warm-up.  MI355X
+  // (profiles/r15/bench_factor_sweep.log), KF = 4, Wm = 1 / Wm = 12, 16 / 100 / T_m chunks:
+  // 100,000 assets 1.75 / 1.69 / 1.67 ms and 14.18 / 12.14 / 12.01 ms; 5,000 assets 0.084 / 0.068 /
+  // 0.073 ms and 0.480 / 0.486 / 0.464 ms
+  int64_t G = g_tune_dfmodel_chunks;
+  if (G < 1 || G > T_m) G = T_m;
+  if (G > 65535) G = 65535;   // (grid.y)
+  const DfmIn in{NO, SR, SRR, SF, SRF, SFF};
+  const DfmOut o{DBETA, DALPHA, DIVOL, DR2, NOBS};
+  const dim3 grid((unsigned)slices, (unsigned)G);
+  switch (KF) {
+    case 1: dfm_launch<1>(ctx, grid, in, T_m, N, Wm, min_obs, (int)G, o); break;
+    case 2: dfm_launch<2>(ctx, grid, in, T_m, N, Wm, min_obs, (int)G, o); break;
+    case 3: dfm_launch<3>(ctx, grid, in, T_m, N, Wm, min_obs, (int)G, o); break;
+    default: dfm_launch<4>(ctx, grid, in, T_m, N, Wm, min_obs, (int)G, o); break;
+  }
+  LAUNCH_CHECK(ctx, "k_daily_fmodel");
   return CSM_OK;
 }
 

@@ -15,9 +15,14 @@
 //                     before its first month and every window is summed again from its oldest
 //                     month, so the chunk count (csm_tune "mm_chunks") only decides how many
 //                     workgroups the launch has: every count gives the same bits.
+//   k_factor_model    MF1..MF5.  k_market_model's shape on KF factors (a template on KF = 1..4):
+//                     the shared factor ring holds a month's KF values side by side, pass 2
+//                     gathers the packed normal equations, fsolve.h solves them per asset-month.
+//                     At KF = 1 every operation is k_market_model's (rule MF8).
 //   k_next_ret        B6.  A lane per asset walks the months with scan.h's rank_step /
 //                     pending_finish on one (psff, prev) pair.
 #include "csm_common.h"
+#include "fsolve.h"
 #include "scan.h"
 
 #define MF_THREADS 256
@@ -31,9 +36,12 @@
 #define NX_TRIP 4        // months per trip of k_next_ret: the next trip's loads are in flight
 
 // the month chunks of k_market_model: 0 auto (mm_auto_chunks) | n >= 1 that many (clamped to T_m)
+// the month chunks of k_factor_model, the same values ("fm_chunks", fm_auto_chunks)
 static int g_tune_mm_chunks = 0;
+static int g_tune_fm_chunks = 0;
 static const TuneKnob g_knobs[] = {
     {"mm_chunks", &g_tune_mm_chunks, [](int v) { return v >= 0; }},
+    {"fm_chunks", &g_tune_fm_chunks, [](int v) { return v >= 0; }},
 };
 
 // B1: the month return over two calendar-adjacent month prices p (month t) and q (month t - 1).
@@ -271,6 +279,221 @@ static inline int mm_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
   return (int)G;
 }
 
+// ---------------------------------------------------------------------------- MF1..MF5
+struct FmOut {
+  double* BETA;   // [KF][T_m][N]
+  double* ALPHA;
+  double* IVOL;
+  double* RESMOM;
+  double* R2;
+  int32_t* NOBS;
+};
+
+// mm_walk on KF factors: f(x, fac[KF]) for cnt entries of the lane's x column and the shared
+// factor ring [W][KF] from slot idx on (wrapping at W), oldest first, MM_BATCH reads in flight.
+template <int KF, class Fn>
+__device__ __forceinline__ void fm_walk(const double* rx, const double* fr, int W, int idx, int cnt,
+                                        Fn f) {
+  int k = 0;
+  for (; k + MM_BATCH <= cnt; k += MM_BATCH) {
+    double x[MM_BATCH], g[MM_BATCH][KF];
+#pragma unroll
+    for (int u = 0; u < MM_BATCH; ++u) {
+      x[u] = rx[idx * MM_THREADS];
+#pragma unroll
+      for (int c = 0; c < KF; ++c) g[u][c] = fr[idx * KF + c];
+      idx = (idx + 1 == W) ? 0 : idx + 1;
+    }
+#pragma unroll
+    for (int u = 0; u < MM_BATCH; ++u) f(x[u], g[u]);
+  }
+  for (; k < cnt; ++k) {
+    double g[KF];
+#pragma unroll
+    for (int c = 0; c < KF; ++c) g[c] = fr[idx * KF + c];
+    f(rx[idx * MM_THREADS], g);
+    idx = (idx + 1 == W) ? 0 : idx + 1;
+  }
+}
+
+// LDS (dynamic): the x ring [Wb][MM_THREADS], then the factor ring [Wb][KF] every lane reads at
+// one address; at most 60 * (64 + 4) * 8 = 32,640 B.
+static inline size_t fm_lds_bytes(int Wb, int KF) {
+  return ((size_t)Wb * MM_THREADS + (size_t)Wb * KF) * sizeof(double);
+}
+
+template <int KF>
+__global__ __launch_bounds__(MM_THREADS) void k_factor_model(
+    const double* __restrict__ PM, const double* __restrict__ F, int T_m, int64_t N, int Wb, int J,
+    int skip, int min_obs, int G, FmOut o) {
+  constexpr int NP = fs_pairs(KF);
+  extern __shared__ __attribute__((aligned(16))) double mm_lds[];
+  const int tid = threadIdx.x;
+  const int64_t a = (int64_t)blockIdx.x * MM_THREADS + tid;
+  if (a >= N) return;   // (no barrier: a lane reads what it wrote itself)
+  double* rx = mm_lds + tid;
+  double* fr = mm_lds + Wb * MM_THREADS;
+  const double NaN = qnan();
+  int m0, m1;
+  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
+  const int j0 = m0 - Wb + 1 > 0 ? m0 - Wb + 1 : 0;   // the chunk starts cold, as k_market_model's
+  double prev = j0 > 0 ? PM[(int64_t)(j0 - 1) * N + a] : NaN;
+  double cur = PM[(int64_t)j0 * N + a];
+  double fcur[KF], fnxt[KF];
+#pragma unroll
+  for (int c = 0; c < KF; ++c) fcur[c] = F[(int64_t)j0 * KF + c];
+  int head = 0;
+  const int kf = Wb - skip - J;   // the formation months' first position in the window (RESMOM)
+  const int64_t plane = (int64_t)T_m * N;
+  for (int j = j0; j < m1; ++j) {
+    double nxt = cur;
+#pragma unroll
+    for (int c = 0; c < KF; ++c) fnxt[c] = fcur[c];
+    if (j + 1 < m1) {
+      nxt = PM[(int64_t)(j + 1) * N + a];
+#pragma unroll
+      for (int c = 0; c < KF; ++c) fnxt[c] = F[(int64_t)(j + 1) * KF + c];
+    }
+    // MF1: a month with a NaN in any factor column has no factor row, and is stored as a month
+    // without x, so the walks test one value
+    bool frow = true;
+#pragma unroll
+    for (int c = 0; c < KF; ++c) frow = frow && !isnan_d(fcur[c]);
+    rx[head * MM_THREADS] = frow ? month_ret(cur, prev) : NaN;
+#pragma unroll
+    for (int c = 0; c < KF; ++c) fr[head * KF + c] = fcur[c];   // every lane: the same values
+    head = (head + 1 == Wb) ? 0 : head + 1;
+    if (j >= m0) {
+      double beta[KF], alpha = NaN, ivol = NaN, resmom = NaN, r2 = NaN;
+#pragma unroll
+      for (int c = 0; c < KF; ++c) beta[c] = NaN;
+      int n = 0;
+      if (j - Wb + 1 >= 0) {   // (uniform) a whole window: both rings are full
+        // MF2, pass 1
+        double sx = 0.0, sf[KF];
+#pragma unroll
+        for (int c = 0; c < KF; ++c) sf[c] = 0.0;
+        fm_walk<KF>(rx, fr, Wb, head, Wb, [&](double x, const double (&f)[KF]) {
+          const bool ok = !isnan_d(x);
+          sx = ok ? sx + x : sx;
+#pragma unroll
+          for (int c = 0; c < KF; ++c) sf[c] = ok ? sf[c] + f[c] : sf[c];
+          n += ok ? 1 : 0;
+        });
+        const double mx = sx / (double)n;
+        double mf[KF];
+#pragma unroll
+        for (int c = 0; c < KF; ++c) mf[c] = sf[c] / (double)n;
+        // pass 2
+        double A[NP], b[KF], cxx = 0.0;
+#pragma unroll
+        for (int p = 0; p < NP; ++p) A[p] = 0.0;
+#pragma unroll
+        for (int c = 0; c < KF; ++c) b[c] = 0.0;
+        fm_walk<KF>(rx, fr, Wb, head, Wb, [&](double x, const double (&f)[KF]) {
+          const bool ok = !isnan_d(x);
+          const double dx = x - mx;
+          double d[KF];
+#pragma unroll
+          for (int c = 0; c < KF; ++c) d[c] = f[c] - mf[c];
+#pragma unroll
+          for (int c = 0; c < KF; ++c) {
+#pragma unroll
+            for (int e = c; e < KF; ++e) {
+              const int p = fs_pair(KF, c, e);
+              A[p] = ok ? A[p] + d[c] * d[e] : A[p];
+            }
+            b[c] = ok ? b[c] + d[c] * dx : b[c];
+          }
+          cxx = ok ? cxx + dx * dx : cxx;
+        });
+        // MF3, MF4
+        double g[KF];
+        const bool solved = fs_solve<KF>(A, b, g);
+        const bool def = n >= min_obs && solved;
+        if (def) {
+          alpha = mx;
+#pragma unroll
+          for (int c = 0; c < KF; ++c) {
+            beta[c] = g[c];
+            alpha = alpha - g[c] * mf[c];
+          }
+        }
+        auto resid = [&](double x, const double (&f)[KF]) {
+          double fit = alpha;
+#pragma unroll
+          for (int c = 0; c < KF; ++c) fit = fit + beta[c] * f[c];
+          return x - fit;
+        };
+        // MF5: the residuals on month j's own coefficients
+        if ((o.IVOL || o.R2) && def && (n >= KF + 2 || cxx > 0.0)) {
+          double se2 = 0.0;
+          fm_walk<KF>(rx, fr, Wb, head, Wb, [&](double x, const double (&f)[KF]) {
+            const bool ok = !isnan_d(x);
+            const double e = resid(x, f);
+            se2 = ok ? se2 + e * e : se2;
+          });
+          if (n >= KF + 2) ivol = sqrt(se2 / ((double)n - (KF + 1.0)));
+          if (cxx > 0.0) r2 = 1.0 - se2 / cxx;
+        }
+        // the residuals again over the J formation months (B5's words)
+        if (o.RESMOM && def) {
+          int h = head + kf;
+          h = h >= Wb ? h - Wb : h;
+          bool all = true;
+          double se = 0.0;
+          fm_walk<KF>(rx, fr, Wb, h, J, [&](double x, const double (&f)[KF]) {
+            all = all && !isnan_d(x);
+            se += resid(x, f);
+          });
+          if (all) {
+            const double me = se / (double)J;
+            double sv = 0.0;
+            fm_walk<KF>(rx, fr, Wb, h, J, [&](double x, const double (&f)[KF]) {
+              const double d = resid(x, f) - me;
+              sv += d * d;
+            });
+            if (sv > 0.0) resmom = se / sqrt(sv / (double)(J - 1));
+          }
+        }
+      }
+      const int64_t oo = (int64_t)j * N + a;
+      if (o.BETA) {
+#pragma unroll
+        for (int c = 0; c < KF; ++c) o.BETA[c * plane + oo] = beta[c];
+      }
+      if (o.ALPHA) o.ALPHA[oo] = alpha;
+      if (o.IVOL) o.IVOL[oo] = ivol;
+      if (o.RESMOM) o.RESMOM[oo] = resmom;
+      if (o.R2) o.R2[oo] = r2;
+      if (o.NOBS) o.NOBS[oo] = n;
+    }
+    prev = cur;
+    cur = nxt;
+#pragma unroll
+    for (int c = 0; c < KF; ++c) fcur[c] = fnxt[c];
+  }
+}
+
+// Auto chunk count of k_factor_model: mm_auto_chunks' rule.  The kernel has k_market_model's
+// shape, warm-up cost and LDS footprint (plus Wb * KF doubles), and the sweep has its shape too.
+// MI355X, Wb = 36, all outputs, KF = 1 / KF = 4 (profiles/r15/bench_factor_sweep.log):
+// 100,000 assets x 461 months 2 / 11 (auto) / 12 / 46 / 150 chunks 4.52 / 3.51 / 3.55 / 3.43 /
+// 4.10 ms and 10.60 / 7.80 / 8.03 / 7.49 / 8.16 ms; 5,000 assets x 300 months 2 / 12 / 46 / 100
+// (auto) / 150 chunks 1.100 / 0.240 / 0.179 / 0.177 / 0.187 ms and 2.023 / 0.483 / 0.373 / 0.349 /
+// 0.356 ms
+static inline int fm_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
+  return mm_auto_chunks(ctx, slices, T_m);
+}
+
+template <int KF>
+static inline void fm_launch(csm_ctx* ctx, dim3 grid, const double* PM, const double* F, int T_m,
+                             int64_t N, int Wb, int J, int skip, int min_obs, int G,
+                             const FmOut& o) {
+  hipLaunchKernelGGL(k_factor_model<KF>, grid, dim3(MM_THREADS), fm_lds_bytes(Wb, KF),
+                     ctx->stream, PM, F, T_m, N, Wb, J, skip, min_obs, G, o);
+}
+
 // --------------------------------------------------------------------------------- B6
 __device__ __forceinline__ void nx_load(double (&x)[NX_TRIP], double (&s)[NX_TRIP],
                                         const double* __restrict__ PM,
@@ -384,6 +607,52 @@ int csm_market_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_
   hipLaunchKernelGGL(k_market_model, dim3((unsigned)slices, (unsigned)G), dim3(MM_THREADS),
                      mm_lds_bytes(Wb), ctx->stream, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o);
   LAUNCH_CHECK(ctx, "k_market_model");
+  return CSM_OK;
+}
+
+int csm_factor_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_m, int64_t N,
+                     int32_t KF, int32_t Wb, int32_t J, int32_t skip, int32_t min_obs,
+                     double* BETA, double* ALPHA, double* IVOL, double* RESMOM, double* R2,
+                     int32_t* NOBS) {
+  int r = prep(ctx);
+  if (r) return r;
+  if (!PM || !F || bad_panel(T_m, N))
+    return set_err(ctx, CSM_E_INVAL, "csm_factor_model: bad arguments (T_m=%d N=%lld)", T_m,
+                   (long long)N);
+  if (KF < 1 || KF > FS_MAXKF)
+    return set_err(ctx, CSM_E_INVAL, "csm_factor_model: KF=%d is outside [1, %d]", KF, FS_MAXKF);
+  if ((int64_t)T_m * KF > ((int64_t)1 << 40) / N)
+    return set_err(ctx, CSM_E_INVAL, "csm_factor_model: bad arguments (T_m=%d N=%lld KF=%d)", T_m,
+                   (long long)N, KF);
+  if (!BETA && !ALPHA && !IVOL && !RESMOM && !R2 && !NOBS)
+    return set_err(ctx, CSM_E_INVAL, "csm_factor_model: no output requested");
+  if (Wb < KF + 1 || Wb > MM_MAXW)
+    return set_err(ctx, CSM_E_INVAL, "csm_factor_model: Wb=%d is outside [KF+1=%d, %d]", Wb,
+                   KF + 1, MM_MAXW);
+  if (min_obs < KF + 1 || min_obs > Wb)
+    return set_err(ctx, CSM_E_INVAL, "csm_factor_model: min_obs=%d is outside [KF+1=%d, Wb=%d]",
+                   min_obs, KF + 1, Wb);
+  if (RESMOM && (J < 2 || skip < 0 || (int64_t)J + skip > Wb))
+    return set_err(ctx, CSM_E_INVAL,
+                   "csm_factor_model: RESMOM needs J >= 2, skip >= 0 and J + skip <= Wb "
+                   "(J=%d skip=%d Wb=%d)", J, skip, Wb);
+  if (!RESMOM) {   // not read
+    J = 2;
+    skip = 0;
+  }
+  const int64_t slices = (N + MM_THREADS - 1) / MM_THREADS;
+  int64_t G = g_tune_fm_chunks > 0 ? g_tune_fm_chunks : fm_auto_chunks(ctx, slices, T_m);
+  if (G > T_m) G = T_m;
+  if (G > 65535) G = 65535;   // (grid.y)
+  const FmOut o{BETA, ALPHA, IVOL, RESMOM, R2, NOBS};
+  const dim3 grid((unsigned)slices, (unsigned)G);
+  switch (KF) {
+    case 1: fm_launch<1>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
+    case 2: fm_launch<2>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
+    case 3: fm_launch<3>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
+    default: fm_launch<4>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
+  }
+  LAUNCH_CHECK(ctx, "k_factor_model");
   return CSM_OK;
 }
 

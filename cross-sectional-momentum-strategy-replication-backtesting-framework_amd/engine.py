@@ -161,6 +161,39 @@ class DailyModelOut:
 
 
 @dataclass
+class FactorModelOut:
+    """csm_factor_model (rules MF1..MF5); None = not asked for."""
+    BETA: torch.Tensor | None = None     # [KF][T_m][N] slopes on the KF factors
+    ALPHA: torch.Tensor | None = None    # [T_m][N] intercept
+    IVOL: torch.Tensor | None = None     # residual standard deviation, n - (KF + 1) degrees
+    RESMOM: torch.Tensor | None = None   # residual momentum on the KF-factor residuals
+    R2: torch.Tensor | None = None       # 1 - residual over total sum of squares
+    NOBS: torch.Tensor | None = None     # int32, observations in the window
+    F: torch.Tensor | None = None        # [T_m][KF] the factors regressed on
+
+
+class DailyFSums(NamedTuple):
+    """csm_daily_fsums (rule MF6): a month's raw moment sums over the days where the asset's
+    daily return r and all KF factors exist; daily_fmodel's input."""
+    NO: torch.Tensor                     # [T_m][N] int32, the observations
+    SR: torch.Tensor                     # [T_m][N] sum of r
+    SRR: torch.Tensor                    # [T_m][N] sum of r * r
+    SF: torch.Tensor                     # [KF][T_m][N] sum of f_k
+    SRF: torch.Tensor                    # [KF][T_m][N] sum of r * f_k
+    SFF: torch.Tensor                    # [KF (KF + 1) / 2][T_m][N] sum of f_j * f_k, j <= k
+
+
+@dataclass
+class DailyFModelOut:
+    """csm_daily_fmodel (rule MF7); None = not asked for."""
+    DBETA: torch.Tensor | None = None    # [KF][T_m][N] slopes of the daily returns on the factors
+    DALPHA: torch.Tensor | None = None   # [T_m][N] intercept
+    DIVOL: torch.Tensor | None = None    # residual standard deviation, n - (KF + 1) degrees
+    DR2: torch.Tensor | None = None      # 1 - residual over total sum of squares
+    NOBS: torch.Tensor | None = None     # int32, observations in the window
+
+
+@dataclass
 class XsRegressOut:
     """csm_xs_regress (rules R1..R5): one cross-sectional regression per month."""
     GAMMA: torch.Tensor                  # [T_m][K + 1] intercept, then one slope per signal
@@ -1050,6 +1083,103 @@ class Engine:
                    *(_ptr(o.get(k)) for k in self.DAILY_OUTPUTS))
         return DailyModelOut(**o)
 
+    FACTOR_OUTPUTS = ("BETA", "ALPHA", "IVOL", "RESMOM", "R2", "NOBS")
+
+    def _factors(self, F, T, name):
+        """A [T] or [T][KF] factor panel as [T][KF] (a 1-D series means KF = 1)."""
+        if F.dim() == 1:
+            F = F.unsqueeze(1)
+        if F.dim() != 2 or not 1 <= F.shape[1] <= 4:
+            raise ValueError(f"{name} must be [{T}] or [{T}][KF] with 1 <= KF <= 4, "
+                             f"got {tuple(F.shape)}")
+        _need(F, name, torch.float64, (T, F.shape[1]), self.device)
+        return F
+
+    def factor_model(self, PM, F, window=36, J=12, skip=1, min_obs=None,
+                     outputs=None) -> FactorModelOut:
+        """csm_factor_model (rules MF1..MF5): each asset's month returns regressed on the KF
+        factors F [T_m][KF] (1 <= KF <= 4; a 1-D F means KF = 1) over `window` calendar months --
+        BETA [KF][T_m][N], ALPHA, the idiosyncratic volatility IVOL, the residual momentum RESMOM
+        over the J months that end `skip` months back, R2 and NOBS.  A month with a NaN in any
+        factor column is no observation.  min_obs defaults to max(KF + 1, ceil(2 * window / 3)).
+        outputs: the FactorModelOut fields to compute (default: all).  At KF = 1 the shared
+        outputs are market_model's bit for bit."""
+        T_m, N = PM.shape
+        _need(PM, "PM", torch.float64, (T_m, N), self.device)
+        F = self._factors(F, T_m, "F")
+        KF = F.shape[1]
+        outputs = self.FACTOR_OUTPUTS if outputs is None else tuple(outputs)
+        unknown = set(outputs) - set(self.FACTOR_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = max(KF + 1, -(-2 * window // 3)) if min_obs is None else int(min_obs)
+        o = {k: self.empty((KF, T_m, N) if k == "BETA" else (T_m, N),
+                           torch.int32 if k == "NOBS" else torch.float64) for k in outputs}
+        self._call("csm_factor_model", _ptr(PM), _ptr(F), T_m, N, KF, window, int(J), int(skip),
+                   min_obs, *(_ptr(o.get(k)) for k in self.FACTOR_OUTPUTS))
+        return FactorModelOut(F=F, **o)
+
+    def daily_fsums(self, P, month_start, FD, max_gap=10, max_month_days=None) -> DailyFSums:
+        """csm_daily_fsums (rule MF6): one pass over P for each (month, asset)'s raw moment sums
+        of its daily returns and the KF daily factors FD [T_d][KF] (a 1-D FD means KF = 1)."""
+        T_d, N = P.shape
+        T_m = month_start.numel() - 1
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        FD = self._factors(FD, T_d, "FD")
+        KF = FD.shape[1]
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        NO = self.empty((T_m, N), torch.int32)
+        SR, SRR = self.empty((T_m, N)), self.empty((T_m, N))
+        SF, SRF = self.empty((KF, T_m, N)), self.empty((KF, T_m, N))
+        SFF = self.empty((KF * (KF + 1) // 2, T_m, N))
+        self._call("csm_daily_fsums", _ptr(P), _ptr(FD), T_d, N, KF, _ptr(month_start), T_m,
+                   int(max_month_days), int(max_gap), _ptr(NO), _ptr(SR), _ptr(SRR), _ptr(SF),
+                   _ptr(SRF), _ptr(SFF))
+        return DailyFSums(NO, SR, SRR, SF, SRF, SFF)
+
+    DAILY_FACTOR_OUTPUTS = ("DBETA", "DALPHA", "DIVOL", "DR2", "NOBS")
+
+    def daily_fmodel(self, sums: DailyFSums, window=1, min_obs=None,
+                     outputs=None) -> DailyFModelOut:
+        """csm_daily_fmodel (rule MF7) on daily_fsums' panels over `window` calendar months
+        (1..12): the slopes DBETA [KF][T_m][N], the intercept DALPHA, the idiosyncratic volatility
+        DIVOL, DR2 and NOBS.  min_obs counts days (default max(15 * window, KF + 1)).  outputs:
+        the DailyFModelOut fields to compute (default: all).  The Dimson beta is DBETA.sum(0) of
+        a model on lagged(MKTD, lags)."""
+        T_m, N = sums.SR.shape
+        KF = sums.SF.shape[0]
+        _need(sums.NO, "NO", torch.int32, (T_m, N), self.device)
+        for k, lead in (("SR", ()), ("SRR", ()), ("SF", (KF,)), ("SRF", (KF,)),
+                        ("SFF", (KF * (KF + 1) // 2,))):
+            _need(getattr(sums, k), k, torch.float64, (*lead, T_m, N), self.device)
+        outputs = self.DAILY_FACTOR_OUTPUTS if outputs is None else tuple(outputs)
+        unknown = set(outputs) - set(self.DAILY_FACTOR_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = max(15 * window, KF + 1) if min_obs is None else int(min_obs)
+        o = {k: self.empty((KF, T_m, N) if k == "DBETA" else (T_m, N),
+                           torch.int32 if k == "NOBS" else torch.float64) for k in outputs}
+        self._call("csm_daily_fmodel", *(_ptr(t) for t in sums), T_m, N, KF, window, min_obs,
+                   *(_ptr(o.get(k)) for k in self.DAILY_FACTOR_OUTPUTS))
+        return DailyFModelOut(**o)
+
+    @staticmethod
+    def lagged(F, lags):
+        """[T][1 + lags]: column k is the series F [T] shifted down k rows, NaN in its first k
+        rows.  The Dimson (1979) beta with `lags` lags is DBETA.sum(0) of
+        daily_fmodel(daily_fsums(P, month_start, lagged(MKTD, lags)))."""
+        lags = int(lags)
+        if F.dim() != 1 or lags < 0:
+            raise ValueError("lagged takes a 1-D series and lags >= 0")
+        out = torch.full((F.shape[0], 1 + lags), float("nan"), dtype=F.dtype, device=F.device)
+        for k in range(1 + lags):
+            out[k:, k] = F[:F.shape[0] - k]
+        return out
+
     def xs_regress(self, Y, signals, W=None, standardize=False, ridge=0.0,
                    min_obs=None) -> XsRegressOut:
         """csm_xs_regress (rules R1..R5): each month's regression of Y [T_m][N] on the K signals
@@ -1709,8 +1839,10 @@ class Engine:
                 out[n] = getattr(dm, self.DAILY_SIGNALS[n])
         return out
 
+    DAILY_FACTOR_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL"}   # the daily signals factors= serves
+
     def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
-                   min_obs=None) -> PipelineOut:
+                   min_obs=None, factors=None) -> PipelineOut:
         """One full pass ranked on a signal of the daily panel: "high52", the month-end price
         over the highest daily price of the last `window` months (no momentum scan), or
         "mom_vol", mom_J over the realised daily volatility of the last `window` months.
@@ -1723,11 +1855,34 @@ class Engine:
         Or on a signal of the daily returns against the equal-weight daily market (rules
         V1..V6): "dbeta", "divol", "dskew" or "max".  For these a `window` left at its default
         means 12 months for "dbeta" and 1 month for the other three, and min_obs counts days
-        (default 15 * window)."""
+        (default 15 * window).
+        factors (rules MF1..MF8): a [T_m][KF] tensor with "resid_mom" / "beta" / "ivol", or a
+        [T_d][KF] tensor with "dbeta" / "divol", replaces the equal-weight market by the caller's
+        KF factors (1 <= KF <= 4); "beta" and "dbeta" rank on column 0's slope, and min_obs
+        defaults to factor_model's / daily_fmodel's.  Any other signal with factors raises."""
         if signal not in self.RUN_SIGNALS:
             raise ValueError(f"signal must be one of {self.RUN_SIGNALS}, got {signal!r}")
+        if factors is not None and signal not in (*self.MARKET_SIGNALS,
+                                                  *self.DAILY_FACTOR_SIGNALS):
+            raise ValueError(f"factors go with {(*self.MARKET_SIGNALS, *self.DAILY_FACTOR_SIGNALS)}"
+                             f", got {signal!r}")
         st = self.month_stats(P, month_start)
-        if signal in self.DAILY_SIGNALS:
+        if factors is not None and signal in self.MARKET_SIGNALS:
+            field = self.MARKET_SIGNALS[signal]
+            fm = self.factor_model(st.PM, factors, window=36 if window == 12 else window, J=J,
+                                   skip=skip, min_obs=min_obs, outputs=(field,))
+            S = getattr(fm, field)
+            S = S[0] if S.dim() == 3 else S          # "beta": column 0's slope
+            NR = self.next_ret(st.PM, S)
+        elif factors is not None:
+            field = self.DAILY_FACTOR_SIGNALS[signal]
+            w = (12 if signal == "dbeta" else 1) if window == 12 else int(window)
+            dm = self.daily_fmodel(self.daily_fsums(P, month_start, factors), w, min_obs,
+                                   outputs=(field,))
+            S = getattr(dm, field)
+            S = S[0] if S.dim() == 3 else S          # "dbeta": column 0's slope
+            NR = self.next_ret(st.PM, S)
+        elif signal in self.DAILY_SIGNALS:
             S = self.daily_signals(P, month_start, (signal,), None if window == 12 else window,
                                    min_obs)[signal]
             NR = self.next_ret(st.PM, S)

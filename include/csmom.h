@@ -84,7 +84,9 @@ int csm_abi_version(void);
  * month chunks: 0 auto, one month each | n >= 1 that many, clamped to T_m), "mm_chunks"
  * (csm_market_model's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits),
  * "dmkt_chunk_days" / "dsums_chunks" / "dmodel_chunks" (csm_daily_market's day rows per
- * workgroup, csm_daily_sums's and csm_daily_model's month chunks: 0 auto; the same bits).
+ * workgroup, csm_daily_sums's and csm_daily_model's month chunks: 0 auto; the same bits),
+ * "fm_chunks" / "dfsums_chunks" / "dfmodel_chunks" (csm_factor_model's, csm_daily_fsums's and
+ * csm_daily_fmodel's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -780,6 +782,94 @@ int csm_daily_model(csm_ctx* ctx, const int32_t* NO, const double* SR, const dou
                     const double* RMAX, int32_t T_m, int64_t N, int32_t Wm, int32_t min_obs,
                     double* DBETA, double* DIVOL, double* DTVOL, double* DSKEW, double* DMAX,
                     int32_t* NOBS);
+
+/*
+ * Multi-factor rolling models (rules MF1..MF8 in DESIGN.md section 7; no reference counterpart):
+ * the KF-factor form of csm_market_model and of csm_daily_sums / csm_daily_model, 1 <= KF <= 4 --
+ * three-factor residual momentum (Blitz, Huij and Martens 2011), idiosyncratic volatility on the
+ * three Fama-French factors (Ang, Hodrick, Xing and Zhang 2006), four-factor alphas, and Dimson
+ * betas (a regression on the market and its lags).  fp64 throughout; every sum is sequential in the
+ * stated order from 0.0 with one rounding per written operation, so two calls, and every launch
+ * shape, give the same bits.  Factor panels are row-major with a date's factors adjacent: F
+ * [T_m][KF] (monthly), FD [T_d][KF] (daily).  A date where any of the KF values is NaN has no
+ * factor row and gives no observation for any asset.
+ *
+ * The solve (MF3) of A g = b, A symmetric KF x KF (A_ij for i > j means A_ji), sequential LDL^T:
+ *   for j = 0 .. KF-1:  d = A_jj, then d = d - (L_jp * L_jp) * D_p for p = 0 .. j-1 ascending;
+ *       the cell is undefined unless A_jj > 0 and d > A_jj * 2^-40;  D_j = d;
+ *       for i = j+1 .. KF-1:  v = A_ji, then v = v - (L_ip * L_jp) * D_p for p < j ascending,
+ *       L_ij = v / D_j
+ *   forward: z_j = b_j, then z_j = z_j - L_jp * z_p for p < j ascending
+ *   back, j = KF-1 .. 0: g_j = z_j / D_j, then g_j = g_j - L_pj * g_p for p = j+1 .. KF-1 ascending
+ *   (KF = 1: g_0 = b_0 / A_00)
+ *
+ * csm_factor_model (MF1..MF5) over the Wb calendar months j = t-Wb+1 .. t (t-Wb+1 >= 0), x[j] the
+ * month return of csm_market_factor's X (computed from PM), f_k = F[j][k]:
+ *   observations: the window's months where x[j] is not NaN and month j has a factor row; n their
+ *       number;  NOBS[t] = n (int32; 0 before the first whole window)
+ *   pass 1, oldest first: sx += x, sf_k += f_k;  mx = sx / n, mf_k = sf_k / n
+ *   pass 2, oldest first: dx = x - mx, d_k = f_k - mf_k;  A_jk += d_j * d_k (j <= k),
+ *       b_k += d_k * dx, cxx += dx * dx
+ *   BETA_k[t] = g_k (MF3);  ALPHA[t] = mx, then ALPHA = ALPHA - g_k * mf_k for k ascending: both
+ *       defined iff n >= min_obs and MF3 is defined
+ *   fit = ALPHA, then fit = fit + g_k * f_k[j] for k ascending;  e[j] = x[j] - fit, with month t's
+ *       coefficients;  se2 = sum e[j]^2 over the observations, oldest first
+ *   IVOL[t] = sqrt(se2 / (n - (KF + 1))): defined iff the coefficients are and n >= KF + 2
+ *   R2[t] = 1 - se2 / cxx: defined iff the coefficients are and cxx > 0
+ *   RESMOM[t]: csm_market_model's RESMOM on these residuals (formation months t-skip-J+1 ..
+ *       t-skip, all J observed, sv > 0)
+ *   KF + 1 <= Wb <= 60;  min_obs in [KF + 1, Wb];  J >= 2, skip >= 0 and J + skip <= Wb, checked
+ *   only when RESMOM is requested;  T_m >= 1;  any N >= 1
+ *   BETA [KF][T_m][N] out; ALPHA, IVOL, RESMOM, R2 [T_m][N] out; NOBS [T_m][N] int32 out: NaN where
+ *       not defined; every one nullable, at least one given
+ * The launch is csm_market_model's; "fm_chunks" (csm_tune: 0 auto | n >= 1 month chunks, clamped to
+ * T_m) only changes how many workgroups there are.
+ *
+ * csm_daily_fsums (MF6): per (month t, asset), over the days d of [month_start[t],
+ * month_start[t+1]) where csm_daily_market's r[d][a] is not NaN and day d has a factor row, in day
+ * order from 0:  NO += 1, SR += r, SRR += r * r, SF_k += f_k, SRF_k += r * f_k,
+ * SFF_p += f_j * f_k for j <= k with p(j, k) = j * KF - j * (j - 1) / 2 + (k - j).
+ *   NO [T_m][N] int32 out; SR, SRR [T_m][N] out; SF, SRF [KF][T_m][N] out;
+ *   SFF [KF (KF + 1) / 2][T_m][N] out; none nullable.  A month without a day gives zeros.
+ *   max_gap, max_month_days and the rows read are csm_daily_sums's.  At KF <= 2 even N with 16-B
+ *   aligned P and outputs (8-B NO) takes two assets per lane, as csm_daily_sums; KF >= 3 takes one
+ *   (the accumulators of two would leave a SIMD one wave); the same bits either way.
+ *   "dfsums_chunks" (csm_tune: 0 auto | n >= 1 month chunks, clamped to T_m) only changes how many
+ *   workgroups there are.
+ *
+ * csm_daily_fmodel (MF7) over the Wm calendar months j = t-Wm+1 .. t (t-Wm+1 >= 0): each MF6 sum
+ * added over j oldest first from 0.0, n the summed NO, nf = (double)n:
+ *   mr = SR / nf, mf_k = SF_k / nf;  A_jk = SFF_p(j,k) - SF_j * mf_k (j <= k),
+ *   b_k = SRF_k - SR * mf_k, crr = SRR - SR * mr
+ *   DBETA_k = g_k (MF3): defined iff n >= min_obs and MF3 is defined
+ *   DALPHA = mr, then DALPHA = DALPHA - g_k * mf_k for k ascending: defined iff DBETA is
+ *   q = crr, then q = q - g_k * b_k for k ascending;  q+ = q < 0 ? 0 : q
+ *   DIVOL = sqrt(q+ / (nf - (KF + 1))): defined iff DBETA is and n >= KF + 2
+ *   DR2 = 1 - q+ / crr: defined iff DBETA is and crr > 0
+ *   NOBS = n (int32; 0 before the first whole window)
+ *   1 <= Wm <= 12;  min_obs >= KF + 1 (days);  T_m >= 1;  any N >= 1
+ *   DBETA [KF][T_m][N] out; DALPHA, DIVOL, DR2 [T_m][N] out; NOBS [T_m][N] int32 out: NaN where not
+ *       defined; every one nullable, at least one given; every input required
+ * "dfmodel_chunks" (csm_tune: 0 auto, one month per chunk | n >= 1 that many, clamped to T_m) only
+ * changes how many workgroups there are; only the sums a requested output depends on are read.
+ *
+ * MF8: at KF = 1 with the same F / FD, csm_factor_model gives csm_market_model's BETA, ALPHA, IVOL,
+ * RESMOM and NOBS, csm_daily_fsums gives csm_daily_sums's NO, SR, SF, SRR, SFF and SRF, and
+ * csm_daily_fmodel gives csm_daily_model's DBETA, DIVOL and NOBS, all bit for bit.
+ * +-inf and zero or negative prices are out of contract.
+ */
+int csm_factor_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_m, int64_t N,
+                     int32_t KF, int32_t Wb, int32_t J, int32_t skip, int32_t min_obs,
+                     double* BETA, double* ALPHA, double* IVOL, double* RESMOM, double* R2,
+                     int32_t* NOBS);
+int csm_daily_fsums(csm_ctx* ctx, const double* P, const double* FD, int64_t T_d, int64_t N,
+                    int32_t KF, const int64_t* month_start, int32_t T_m, int32_t max_month_days,
+                    int32_t max_gap, int32_t* NO, double* SR, double* SRR, double* SF, double* SRF,
+                    double* SFF);
+int csm_daily_fmodel(csm_ctx* ctx, const int32_t* NO, const double* SR, const double* SRR,
+                     const double* SF, const double* SRF, const double* SFF, int32_t T_m,
+                     int64_t N, int32_t KF, int32_t Wm, int32_t min_obs, double* DBETA,
+                     double* DALPHA, double* DIVOL, double* DR2, int32_t* NOBS);
 
 /*
  * Fama-MacBeth (1973) cross-sectional regressions (rules R1..R6 in DESIGN.md section 7; the
