@@ -34,12 +34,16 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.factor_model / daily_fsums     KF-factor rolling models, KF = 1..4: FF3-style betas, alphas,
   Engine.daily_fmodel / lagged          idiosyncratic volatility, residual momentum, Dimson betas
   residual_momentum / align_factors     (rules MF1..MF8)
+  Engine.liq_sums / liq_model           Amihud illiquidity, dollar average daily volume, turnover,
+  liquidity_signals                     zero-return and zero-volume days from the daily price and
+                                        volume panels (rules Q1..Q6)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyFModelOut, DailyFSums, DailyModelOut, DailyOut, DailySums, Engine, FactorModelOut, FamaMacBethOut, GroupStatsOut, ICDecayOut, MarketModelOut,
+from .engine import (DailyFModelOut, DailyFSums, DailyModelOut, DailyOut, DailySums, Engine, FactorModelOut, FamaMacBethOut, GroupStatsOut, ICDecayOut, LiqModelOut, LiqSums,
+                     MarketModelOut,
                      MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RankICOut, SignalsOut,
                      XsRegressOut, absent_tensor, is_absent, quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
@@ -51,6 +55,7 @@ from .universe import UniverseResult, breakpoint_mask, shares_row, universe_mome
 from .factors import ResidualMomentumResult, align_factors, residual_momentum
 from .regress import FamaMacBethResult, fama_macbeth
 from .ic import ICResult, information_coefficient
+from .liquidity import LIQUIDITY_COLUMNS, liquidity_signals
 from .panel import DensePanel, from_long, month_offsets, monthly_frame
 from .replication import (ReplicationResult, assign_deciles_per_date, daily_portfolio_returns,
                           monthly_replication)
@@ -72,5 +77,5 @@ __all__ = [
     "RankICOut", "ICDecayOut", "ICResult", "information_coefficient",
     "UniverseResult", "breakpoint_mask", "shares_row", "universe_momentum",
     "FactorModelOut", "DailyFSums", "DailyFModelOut", "ResidualMomentumResult", "align_factors",
-    "residual_momentum",
+    "residual_momentum", "LiqSums", "LiqModelOut", "LIQUIDITY_COLUMNS", "liquidity_signals",
 ]

@@ -111,6 +111,10 @@ SIGNATURES = {
                                        _p, _p, _p, _p]),
     "csm_daily_fmodel": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _i32,
                                         _p, _p, _p, _p, _p]),
+    "csm_liq_sums": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i32, _i32, _i32, _p, _p, _p, _p,
+                                    _p, _p, _p, _p]),
+    "csm_liq_model": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32,
+                                     _i32, _f64, _p, _p, _p, _p, _p, _p]),
     "csm_xs_regress": (ctypes.c_int, [_p, _p, _p, _i32, _p, _i32, _i64, _i32, _f64, _i32, _p, _p,
                                       _p]),
     "csm_newey_west": (ctypes.c_int, [_p, _p, _i32, _i32, _i64, _i32, _p, _p, _p, _p]),

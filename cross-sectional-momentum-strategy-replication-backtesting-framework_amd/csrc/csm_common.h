@@ -174,6 +174,7 @@ int csm_tune_signals(const char* key, int value);     // signals.hip
 int csm_tune_market(const char* key, int value);      // market.hip
 int csm_tune_groups(const char* key, int value);      // groups.hip
 int csm_tune_dailymkt(const char* key, int value);    // dailymkt.hip
+int csm_tune_liq(const char* key, int value);         // liquidity.hip
 }
 // The fused month-end + scan launch behind every csm_signal* entry point and csm_pipeline
 // (signal.hip): k_signal_tail or k_signal for the panel's width and alignment and the signal

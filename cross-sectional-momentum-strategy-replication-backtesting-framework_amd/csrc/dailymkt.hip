@@ -33,6 +33,7 @@
 //                     chunk count (csm_tune "dmodel_chunks") only decides how many workgroups
 //                     there are.
 #include "csm_common.h"
+#include "dayret.h"
 #include "daytrip.h"
 #include "fsolve.h"
 #include "scan.h"
@@ -42,7 +43,6 @@
 #define DM_SLICE (DM_THREADS * DM_PER)
 #define DM_WAVES (DM_THREADS / 64)
 #define DM_TRIP 4        // day rows per trip: two trips of eight assets are 128 VGPRs of buffers
-#define DM_MAXGAP 32
 #define DMD_THREADS 64
 #define DMD_MAXW 12
 // k_daily_fsums: the largest KF that takes two assets per lane and loads its factor rows a trip
@@ -74,57 +74,6 @@ static const TuneKnob g_knobs[] = {
     {"dfsums_chunks", &g_tune_dfsums_chunks, [](int v) { return v >= 0; }},
     {"dfmodel_chunks", &g_tune_dfmodel_chunks, [](int v) { return v >= 0; }},
 };
-
-// ------------------------------------------------------------------------------- V1
-// One asset's last priced price (NaN: none within reach) and the rows since it, saturated at
-// DM_MAXGAP (one more is past every max_gap).
-struct DrLane {
-  double lp;
-  int age;
-};
-
-// Row d's return: x / lp - 1.0 when x is priced and the last priced row is at most max_gap rows
-// back, else NaN.  A NaN x or lp makes the quotient NaN by itself; the division's operands are a
-// loaded value and a select of loaded values.
-__device__ __forceinline__ double dr_step(DrLane& s, double x, int max_gap) {
-  const bool ok = !isnan_d(x);
-  const int g = s.age + 1;
-  const double r = g <= max_gap ? x / s.lp - 1.0 : qnan();
-  s.lp = ok ? x : s.lp;
-  s.age = ok ? 0 : (g > DM_MAXGAP ? DM_MAXGAP : g);
-  return r;
-}
-
-// The lead-in of a chunk that starts at row d0: each asset's latest priced row among the max_gap
-// rows before d0 (clipped at row 0).  An older one books no return in the chunk.  col(k) is the
-// k-th asset's column, or -1.  Only the lanes still searching load; the walk ends when no lane of
-// the wave is.
-template <int CNT, class Col>
-__device__ __forceinline__ void dr_lead_in(DrLane (&s)[CNT], const double* __restrict__ P,
-                                           int64_t N, int64_t d0, int max_gap, Col col) {
-#pragma unroll
-  for (int k = 0; k < CNT; ++k) {
-    s[k].lp = qnan();
-    s[k].age = DM_MAXGAP;
-  }
-  for (int g = 1; g <= max_gap && d0 - g >= 0; ++g) {
-    bool searching = false;
-#pragma unroll
-    for (int k = 0; k < CNT; ++k) {
-      const int64_t a = col(k);
-      if (a >= 0 && isnan_d(s[k].lp)) {
-        const double x = P[(d0 - g) * N + a];
-        if (!isnan_d(x)) {
-          s[k].lp = x;
-          s[k].age = g - 1;
-        } else {
-          searching = true;
-        }
-      }
-    }
-    if (!__any(searching)) break;
-  }
-}
 
 // ------------------------------------------------------------------------------- V2
 // Rows [d, d + DM_TRIP) of the lane's DM_PER assets; rows from dB on and columns from N on are NaN.

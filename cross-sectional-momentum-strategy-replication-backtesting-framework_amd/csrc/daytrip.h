@@ -1,6 +1,7 @@
 // daytrip.h -- the day-row trips of the kernels that walk a chunk of consecutive months of the
 // daily panel with a lane per asset (or two adjacent ones): k_month_stats (signals.hip, rule D1)
-// and k_daily_sums (dailymkt.hip, rule V3).
+// and k_daily_sums (dailymkt.hip, rule V3); k_liq_sums (liquidity.hip, rule Q2) takes the block size
+// and the clip and loads trips of its own length.
 #pragma once
 #include "csm_common.h"
 

@@ -193,6 +193,30 @@ class DailyFModelOut:
     NOBS: torch.Tensor | None = None     # int32, observations in the window
 
 
+class LiqSums(NamedTuple):
+    """csm_liq_sums (rule Q2), each [T_m][N]: a month's day counts and its volume, dollar volume
+    and Amihud sums; liq_model's input."""
+    NP: torch.Tensor                     # int32, priced days
+    ND: torch.Tensor                     # int32, days with a return (rule V1)
+    NA: torch.Tensor                     # int32, days with a return and a positive dollar volume
+    NZR: torch.Tensor | None             # int32, return days with r == 0
+    NZV: torch.Tensor | None             # int32, priced days with zero volume
+    SV: torch.Tensor | None              # sum of the volume over the priced days
+    SDV: torch.Tensor                    # sum of price * volume over the priced days
+    SIL: torch.Tensor                    # sum of |r| / (price * volume) over the Amihud days
+
+
+@dataclass
+class LiqModelOut:
+    """csm_liq_model (rule Q3), each [T_m][N]; None = not asked for."""
+    ILLIQ: torch.Tensor | None = None    # Amihud (2002): mean |r| / dollar volume, times scale
+    DVOL: torch.Tensor | None = None     # dollar average daily volume (portfolio's ADV)
+    TURN: torch.Tensor | None = None     # average daily volume over shares outstanding
+    ZRET: torch.Tensor | None = None     # share of the return days with a zero return
+    ZVOL: torch.Tensor | None = None     # share of the priced days with zero volume
+    NOBS: torch.Tensor | None = None     # int32, Amihud days in the window
+
+
 @dataclass
 class XsRegressOut:
     """csm_xs_regress (rules R1..R5): one cross-sectional regression per month."""
@@ -1167,6 +1191,64 @@ class Engine:
                    *(_ptr(o.get(k)) for k in self.DAILY_FACTOR_OUTPUTS))
         return DailyFModelOut(**o)
 
+    def liq_sums(self, P, V, month_start, max_gap=10, max_month_days=None, with_sv=True,
+                 with_nzr=True, with_nzv=True) -> LiqSums:
+        """csm_liq_sums (rules Q1, Q2): one pass over the daily prices P and volumes V for each
+        (month, asset)'s priced, return and Amihud day counts, its volume and dollar volume sums
+        and its sum of |r| / dollar volume."""
+        T_d, N = P.shape
+        T_m = month_start.numel() - 1
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        _need(V, "V", torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        NP, ND, NA = (self.empty((T_m, N), torch.int32) for _ in range(3))
+        NZR = self.empty((T_m, N), torch.int32) if with_nzr else None
+        NZV = self.empty((T_m, N), torch.int32) if with_nzv else None
+        SV = self.empty((T_m, N)) if with_sv else None
+        SDV, SIL = self.empty((T_m, N)), self.empty((T_m, N))
+        self._call("csm_liq_sums", _ptr(P), _ptr(V), T_d, N, _ptr(month_start), T_m,
+                   int(max_month_days), int(max_gap), _ptr(NP), _ptr(ND), _ptr(NA), _ptr(NZR),
+                   _ptr(NZV), _ptr(SV), _ptr(SDV), _ptr(SIL))
+        return LiqSums(NP, ND, NA, NZR, NZV, SV, SDV, SIL)
+
+    LIQ_OUTPUTS = ("ILLIQ", "DVOL", "TURN", "ZRET", "ZVOL", "NOBS")
+
+    def liq_model(self, sums: LiqSums, window=12, min_obs=None, scale=1e6, SH=None,
+                  outputs=None) -> LiqModelOut:
+        """csm_liq_model (rule Q3) on liq_sums' panels over `window` calendar months (1..12):
+        Amihud's ILLIQ (times scale), the dollar average daily volume DVOL (portfolio's ADV), the
+        turnover TURN on the shares outstanding SH [T_m][N], the shares of zero-return and
+        zero-volume days ZRET and ZVOL, and NOBS.  min_obs counts days (default 15 * window).
+        outputs: the LiqModelOut fields to compute (default: all the sums and SH given allow)."""
+        T_m, N = sums.SDV.shape
+        for k in ("NP", "ND", "NA", "NZR", "NZV"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.int32, (T_m, N), self.device)
+        for k in ("SV", "SDV", "SIL"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.float64, (T_m, N), self.device)
+        if SH is not None:
+            _need(SH, "SH", torch.float64, (T_m, N), self.device)
+        if outputs is None:
+            outputs = tuple(k for k in self.LIQ_OUTPUTS
+                            if not (k == "TURN" and (SH is None or sums.SV is None))
+                            and not (k == "ZRET" and sums.NZR is None)
+                            and not (k == "ZVOL" and sums.NZV is None))
+        unknown = set(outputs) - set(self.LIQ_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = 15 * window if min_obs is None else int(min_obs)
+        o = {k: self.empty((T_m, N), torch.int32 if k == "NOBS" else torch.float64)
+             for k in outputs}
+        self._call("csm_liq_model", *(_ptr(t) for t in sums), _ptr(SH), T_m, N, window, min_obs,
+                   float(scale), *(_ptr(o.get(k)) for k in self.LIQ_OUTPUTS))
+        return LiqModelOut(**o)
+
     @staticmethod
     def lagged(F, lags):
         """[T][1 + lags]: column k is the series F [T] shifted down k rows, NaN in its first k
@@ -1356,7 +1438,7 @@ class Engine:
                    *(_ptr(o.get(k)) for k in self.GROUP_OUTPUTS))
         return GroupStatsOut(**o)
 
-    def _signal_panels(self, P, month_start, signal, J, skip, n_bins, window, min_obs):
+    def _signal_panels(self, P, month_start, signal, J, skip, n_bins, window, min_obs, V=None):
         """(PM, S, NR) of a signal name: "mom" as run builds it, the others as run_signal does."""
         if signal == "mom":
             PM, _ = self.month_end(P, month_start)
@@ -1366,20 +1448,22 @@ class Engine:
             else:
                 _, S, NR = self.momentum(PM, J, skip)
         else:
-            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs)
+            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs, V=V)
             PM, S, NR = r.PM, r.M, r.NR
         return PM, S, NR
 
     def run_neutral(self, P, month_start, GID, n_groups, signal="mom", adjust=None, J=12, skip=1,
-                    n_bins=10, min_group=1, window=12, min_obs=None) -> PipelineOut:
+                    n_bins=10, min_group=1, window=12, min_obs=None, V=None) -> PipelineOut:
         """One full pass ranked inside groups (Moskowitz-Grinblatt 1999).  The signal is built as
         run (signal "mom") or run_signal (its names) build it.  adjust None: labels by
         deciles_within, the decile means pooled over the groups.  adjust "demean" / "zscore": the
         signal minus its group's mean (over its deviation), rule N5, then a plain deciles on it.
-        M is the signal ranked and NR the signal's next return (rule N6)."""
+        M is the signal ranked and NR the signal's next return (rule N6).  V: the daily volume
+        panel, for run_signal's liquidity names."""
         if adjust not in (None, "demean", "zscore"):
             raise ValueError(f"adjust must be None, 'demean' or 'zscore', got {adjust!r}")
-        PM, S, NR = self._signal_panels(P, month_start, signal, J, skip, n_bins, window, min_obs)
+        PM, S, NR = self._signal_panels(P, month_start, signal, J, skip, n_bins, window, min_obs,
+                                        V)
         if adjust is None:
             L, EW, CNT, NV = self.deciles_within(S, NR, GID, n_groups, n_bins, min_group,
                                                  with_nv=True)
@@ -1818,7 +1902,8 @@ class Engine:
 
     MARKET_SIGNALS = {"resid_mom": "RESMOM", "beta": "BETA", "ivol": "IVOL"}
     DAILY_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL", "dskew": "DSKEW", "max": "DMAX"}
-    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS)
+    LIQ_SIGNALS = {"illiq": "ILLIQ", "dvol": "DVOL", "zret": "ZRET"}
+    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS, *LIQ_SIGNALS)
 
     def daily_signals(self, P, month_start, names, window=None, min_obs=None, max_gap=10):
         """{name: [T_m][N]} for names of DAILY_SIGNALS (rules V1..V4): the daily market, one pass
@@ -1839,10 +1924,21 @@ class Engine:
                 out[n] = getattr(dm, self.DAILY_SIGNALS[n])
         return out
 
+    def liq_signals(self, P, V, month_start, names, window=None, min_obs=None, max_gap=10,
+                    scale=1e6):
+        """{name: [T_m][N]} for names of LIQ_SIGNALS (rules Q1..Q3): one pass over both panels
+        for the month sums and one model call.  window None: 12 months; min_obs counts days
+        (default 15 * window)."""
+        sums = self.liq_sums(P, V, month_start, max_gap, with_sv=False,
+                             with_nzr="zret" in names, with_nzv=False)
+        lm = self.liq_model(sums, 12 if window is None else int(window), min_obs, scale,
+                            outputs=tuple(self.LIQ_SIGNALS[n] for n in names))
+        return {n: getattr(lm, self.LIQ_SIGNALS[n]) for n in names}
+
     DAILY_FACTOR_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL"}   # the daily signals factors= serves
 
     def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
-                   min_obs=None, factors=None) -> PipelineOut:
+                   min_obs=None, factors=None, V=None) -> PipelineOut:
         """One full pass ranked on a signal of the daily panel: "high52", the month-end price
         over the highest daily price of the last `window` months (no momentum scan), or
         "mom_vol", mom_J over the realised daily volatility of the last `window` months.
@@ -1859,9 +1955,16 @@ class Engine:
         factors (rules MF1..MF8): a [T_m][KF] tensor with "resid_mom" / "beta" / "ivol", or a
         [T_d][KF] tensor with "dbeta" / "divol", replaces the equal-weight market by the caller's
         KF factors (1 <= KF <= 4); "beta" and "dbeta" rank on column 0's slope, and min_obs
-        defaults to factor_model's / daily_fmodel's.  Any other signal with factors raises."""
+        defaults to factor_model's / daily_fmodel's.  Any other signal with factors raises.
+        Or on a liquidity signal of the daily prices and the daily volume panel V [T_d][N] (rules
+        Q1..Q6): "illiq", "dvol" or "zret" over `window` months, min_obs counting days (default
+        15 * window).  These three need V; V with factors raises."""
         if signal not in self.RUN_SIGNALS:
             raise ValueError(f"signal must be one of {self.RUN_SIGNALS}, got {signal!r}")
+        if signal in self.LIQ_SIGNALS and V is None:
+            raise ValueError(f"signal {signal!r} needs the daily volume panel V")
+        if V is not None and factors is not None:
+            raise ValueError("V and factors do not go together")
         if factors is not None and signal not in (*self.MARKET_SIGNALS,
                                                   *self.DAILY_FACTOR_SIGNALS):
             raise ValueError(f"factors go with {(*self.MARKET_SIGNALS, *self.DAILY_FACTOR_SIGNALS)}"
@@ -1885,6 +1988,9 @@ class Engine:
         elif signal in self.DAILY_SIGNALS:
             S = self.daily_signals(P, month_start, (signal,), None if window == 12 else window,
                                    min_obs)[signal]
+            NR = self.next_ret(st.PM, S)
+        elif signal in self.LIQ_SIGNALS:
+            S = self.liq_signals(P, V, month_start, (signal,), window, min_obs)[signal]
             NR = self.next_ret(st.PM, S)
         elif signal in self.MARKET_SIGNALS:
             field = self.MARKET_SIGNALS[signal]

@@ -10,6 +10,7 @@ from dataclasses import dataclass
 import numpy as np
 import pandas as pd
 
+from .engine import Engine
 from .features import get_engine, upload_panel
 from .panel import from_long
 from .regress import build_signals
@@ -47,8 +48,8 @@ def information_coefficient(daily_df, signals=("mom", "high52", "beta", "ivol"),
     if panel.P.size == 0 or panel.T_m == 0:
         return None
     eng = get_engine(device)
-    P, _, ms = upload_panel(panel, eng, with_volume=False)
-    S, X = build_signals(eng, P, ms, names, J, skip, window)
+    P, V, ms = upload_panel(panel, eng, with_volume=any(n in Engine.LIQ_SIGNALS for n in names))
+    S, X = build_signals(eng, P, ms, names, J, skip, window, V=V)
     idx = pd.DatetimeIndex(panel.month_end, name="date")
     cols, ric, pic, nobs, rows = [], [], [], [], []
     used = 0

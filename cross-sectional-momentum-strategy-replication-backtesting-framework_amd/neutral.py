@@ -59,12 +59,12 @@ def neutral_momentum(daily_df, groups, J=12, skip=1, n_bins=10, K=1, min_group=N
     if not names:
         raise ValueError("no ticker of the frame has a group")
     eng = get_engine(device)
-    P, _, ms = upload_panel(panel, eng, with_volume=False)
+    P, V, ms = upload_panel(panel, eng, with_volume=signal in eng.LIQ_SIGNALS)
     GID = torch.from_numpy(gid).to(eng.device)
     G = len(names)
     mg = int(n_bins) if min_group is None else int(min_group)
     out = eng.run_neutral(P, ms, GID, G, signal=signal, adjust=adjust, J=J, skip=skip,
-                          n_bins=n_bins, min_group=mg)
+                          n_bins=n_bins, min_group=mg, V=V)
     EW, LS = out.EW, out.LS
     if K > 1:
         pf = eng.portfolio(out.L, out.NR, n_bins, K=K, with_costs=False)

@@ -27,14 +27,18 @@ class FamaMacBethResult:
     lags: int
 
 
-def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None):
+def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None, V=None):
     """The named signals of a daily panel on the device, each [T_m][N], with the B1 month return
     X: "mom" (mom_J), "rev" (the month's own return) and Engine.RUN_SIGNALS' names, built by the
     calls run_signal makes.  window None: 12 months for "high52" / "mom_vol" and "dbeta", 36 for
-    the monthly market model's, 1 for "divol", "dskew" and "max"."""
+    the monthly market model's, 1 for "divol", "dskew" and "max", 12 for the liquidity names
+    "illiq", "dvol" and "zret", which need the daily volume panel V [T_d][N]."""
     unknown = [n for n in names if n not in SIGNAL_NAMES]
     if unknown:
         raise ValueError(f"signals must be among {SIGNAL_NAMES}, got {unknown}")
+    liq = [n for n in names if n in Engine.LIQ_SIGNALS]
+    if liq and V is None:
+        raise ValueError(f"signals {liq} need the daily volume panel V")
     st = eng.month_stats(P, month_start)
     _, _, X = eng.market_factor(st.PM, with_x=True)
     out = {}
@@ -60,6 +64,8 @@ def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None)
     dsig = [n for n in names if n in Engine.DAILY_SIGNALS]
     if dsig:
         out.update(eng.daily_signals(P, month_start, dsig, window))
+    if liq:
+        out.update(eng.liq_signals(P, V, month_start, liq, window))
     return [out[n] for n in names], X
 
 
@@ -78,8 +84,8 @@ def fama_macbeth(daily_df, signals=("mom", "high52", "beta", "ivol"), J=12, skip
     if panel.P.size == 0 or panel.T_m == 0:
         return None
     eng = get_engine(device)
-    P, _, ms = upload_panel(panel, eng, with_volume=False)
-    S, X = build_signals(eng, P, ms, names, J, skip, window)
+    P, V, ms = upload_panel(panel, eng, with_volume=any(n in Engine.LIQ_SIGNALS for n in names))
+    S, X = build_signals(eng, P, ms, names, J, skip, window, V=V)
     if transform == "rank":
         S = [eng.xs_rank(s, pct=True) for s in S]
     Y = torch.cat([X[1:], torch.full_like(X[:1], float("nan"))])

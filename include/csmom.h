@@ -86,7 +86,10 @@ int csm_abi_version(void);
  * "dmkt_chunk_days" / "dsums_chunks" / "dmodel_chunks" (csm_daily_market's day rows per
  * workgroup, csm_daily_sums's and csm_daily_model's month chunks: 0 auto; the same bits),
  * "fm_chunks" / "dfsums_chunks" / "dfmodel_chunks" (csm_factor_model's, csm_daily_fsums's and
- * csm_daily_fmodel's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits).
+ * csm_daily_fmodel's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits),
+ * "lsums_chunks" / "lmodel_chunks" (csm_liq_sums's and csm_liq_model's month chunks: 0 auto |
+ * n >= 1 that many, clamped to T_m), "lsums_pair" (csm_liq_sums: 0 one asset per lane | 1 two
+ * where the panels allow; the same bits from all three).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -870,6 +873,64 @@ int csm_daily_fmodel(csm_ctx* ctx, const int32_t* NO, const double* SR, const do
                      const double* SF, const double* SRF, const double* SFF, int32_t T_m,
                      int64_t N, int32_t KF, int32_t Wm, int32_t min_obs, double* DBETA,
                      double* DALPHA, double* DIVOL, double* DR2, int32_t* NOBS);
+
+/*
+ * Liquidity signals from the daily price and volume panels (rules Q1..Q6 in DESIGN.md section 7; no
+ * reference counterpart): Amihud's (2002) ILLIQ, the mean of |daily return| / daily dollar volume;
+ * the dollar average daily volume csm_portfolio's ADV takes; turnover; and the shares of
+ * zero-return days (Lesmond, Ogden and Trzcinka 1999) and zero-volume days.  fp64 throughout, every
+ * sum sequential in day (then month) order from 0.0 with one rounding per written operation, so two
+ * calls, and every launch shape, give the same bits.
+ *
+ * Q1: P, V [T_d][N].  v[d][a] = V[d][a], a NaN taken as 0.0 (csm_month_end's rule).  A day is
+ * priced when P[d][a] is not NaN (the ABSENT payload counts as NaN); on a priced day dv = P * v, one
+ * multiply.  r[d][a] is csm_daily_market's daily return (V1) with max_gap in [1, 32].  Volume on an
+ * unpriced day is ignored.  Negative or +-inf volume and +-inf or non-positive prices are out of
+ * contract.
+ *
+ * csm_liq_sums (Q2): per (month t, asset), over the days d of [month_start[t], month_start[t+1]) in
+ * day order from 0:
+ *   priced day:                       NP += 1, SV += v, SDV += dv, NZV += (v == 0)
+ *   return day (r not NaN):           ND += 1, NZR += (r == 0.0)
+ *   Amihud day (r not NaN, dv > 0):   NA += 1, SIL += fabs(r) / dv
+ *   NP, ND, NA [T_m][N] int32 out; SDV, SIL [T_m][N] out; NZR, NZV [T_m][N] int32 and SV [T_m][N]
+ *   nullable out.  A month without a day gives zeros.
+ *   max_month_days in [1, 32], csm_month_stats's bound
+ * Any N >= 1, one asset per lane; under csm_tune "lsums_pair" = 1 even N with 16-B aligned P, V and
+ * f64 outputs and 8-B aligned int32 outputs takes two assets per lane (it measured a few per cent
+ * slower, so it is not the default), the same bits.  "lsums_chunks" (csm_tune: 0 auto | n >= 1
+ * month chunks, clamped to T_m) only changes how many workgroups there are.  No row before month_start[0] - max_gap
+ * (clipped to 0) and none at or past month_start[T_m] is read, from either panel; the rows before
+ * month_start[0] are read from P only.
+ *
+ * csm_liq_model (Q3) over the Wm calendar months j = t-Wm+1 .. t (t-Wm+1 >= 0): each Q2 value added
+ * over j oldest first from zero into np, nd, na, nzr, nzv, sv, sdv, sil; counts enter the
+ * arithmetic as (double):
+ *   ILLIQ = (sil / na) * scale: defined iff na >= min_obs;  scale finite and positive
+ *   DVOL  = sdv / np: defined iff np >= min_obs (the dollar ADV of csm_portfolio's ADV)
+ *   TURN  = (sv / np) / SH[t][a]: defined iff np >= min_obs and SH[t][a] > 0
+ *   ZRET  = nzr / nd: defined iff nd >= min_obs
+ *   ZVOL  = nzv / np: defined iff np >= min_obs
+ *   NOBS  = na (int32; 0 before the first whole window)
+ *   1 <= Wm <= 12;  min_obs >= 1 (days);  T_m >= 1;  any N >= 1
+ *   SH [T_m][N] nullable in: shares outstanding (csm_turnover_features' SH, for instance)
+ *   ILLIQ, DVOL, TURN, ZRET, ZVOL [T_m][N] out, NOBS [T_m][N] int32 out: NaN where not defined;
+ *       every one nullable, at least one given; TURN needs SV and SH, ZRET needs NZR and ZVOL needs
+ *       NZV (nullable inputs otherwise)
+ * "lmodel_chunks" (csm_tune: 0 auto, one month per chunk | n >= 1 that many, clamped to T_m) only
+ * changes how many workgroups there are; only the panels a requested output depends on are read.
+ * There is no log(1 + ILLIQ) output: ranks do not change under it.  The next return of any of these
+ * signals is csm_next_ret's (Q4).
+ */
+int csm_liq_sums(csm_ctx* ctx, const double* P, const double* V, int64_t T_d, int64_t N,
+                 const int64_t* month_start, int32_t T_m, int32_t max_month_days, int32_t max_gap,
+                 int32_t* NP, int32_t* ND, int32_t* NA, int32_t* NZR, int32_t* NZV, double* SV,
+                 double* SDV, double* SIL);
+int csm_liq_model(csm_ctx* ctx, const int32_t* NP, const int32_t* ND, const int32_t* NA,
+                  const int32_t* NZR, const int32_t* NZV, const double* SV, const double* SDV,
+                  const double* SIL, const double* SH, int32_t T_m, int64_t N, int32_t Wm,
+                  int32_t min_obs, double scale, double* ILLIQ, double* DVOL, double* TURN,
+                  double* ZRET, double* ZVOL, int32_t* NOBS);
 
 /*
  * Fama-MacBeth (1973) cross-sectional regressions (rules R1..R6 in DESIGN.md section 7; the
