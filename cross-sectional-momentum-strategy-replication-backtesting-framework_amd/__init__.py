@@ -37,6 +37,8 @@ a Python identifier).  Public API (reference file:line it replaces):
   Engine.liq_sums / liq_model           Amihud illiquidity, dollar average daily volume, turnover,
   liquidity_signals                     zero-return and zero-volume days from the daily price and
                                         volume panels (rules Q1..Q6)
+  Engine.range_sums / range_model       Parkinson volatility, Corwin-Schultz and Abdi-Ranaldo bid-ask
+  range_signals                         spreads from the daily high, low and close (rules HL1..HL6)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
@@ -44,7 +46,8 @@ a Python identifier).  Public API (reference file:line it replaces):
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
 from .engine import (DailyFModelOut, DailyFSums, DailyModelOut, DailyOut, DailySums, Engine, FactorModelOut, FamaMacBethOut, GroupStatsOut, ICDecayOut, LiqModelOut, LiqSums,
                      MarketModelOut,
-                     MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RankICOut, SignalsOut,
+                     MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RangeModelOut, RangeSums,
+                     RankICOut, SignalsOut,
                      XsRegressOut, absent_tensor, is_absent, quantile_table)
 from .data import fetch_daily, load_daily_panel, normalize_daily_columns
 from .features import compute_monthly_momentum_from_daily, compute_monthly_turnover, get_engine
@@ -56,7 +59,8 @@ from .factors import ResidualMomentumResult, align_factors, residual_momentum
 from .regress import FamaMacBethResult, fama_macbeth
 from .ic import ICResult, information_coefficient
 from .liquidity import LIQUIDITY_COLUMNS, liquidity_signals
-from .panel import DensePanel, from_long, month_offsets, monthly_frame
+from .ranges import RANGE_COLUMNS, range_signals
+from .panel import DensePanel, from_long, month_offsets, monthly_frame, range_from_long
 from .replication import (ReplicationResult, assign_deciles_per_date, daily_portfolio_returns,
                           monthly_replication)
 from .sweep import SUMMARY_FIELDS, SweepConfig, SweepRunner, strategy_grid
@@ -78,4 +82,5 @@ __all__ = [
     "UniverseResult", "breakpoint_mask", "shares_row", "universe_momentum",
     "FactorModelOut", "DailyFSums", "DailyFModelOut", "ResidualMomentumResult", "align_factors",
     "residual_momentum", "LiqSums", "LiqModelOut", "LIQUIDITY_COLUMNS", "liquidity_signals",
+    "RangeSums", "RangeModelOut", "RANGE_COLUMNS", "range_signals", "range_from_long",
 ]

@@ -167,7 +167,7 @@ int csm_tune_signal_tc(const char* key, int value);   // signal_tc.hip
 int csm_tune_deciles(const char* key, int value);     // deciles_wide.hip
 int csm_tune_ptr_deciles(const char* key, void* p);
 int csm_tune_shards(const char* key, int value);      // shards.hip
-extern "C" {   // (these six are among the library's exported symbols)
+extern "C" {   // (these are among the library's exported symbols)
 int csm_tune_portfolio(const char* key, int value);   // portfolio.hip
 int csm_tune_ptr_portfolio(const char* key, void* p);
 int csm_tune_signals(const char* key, int value);     // signals.hip
@@ -175,6 +175,7 @@ int csm_tune_market(const char* key, int value);      // market.hip
 int csm_tune_groups(const char* key, int value);      // groups.hip
 int csm_tune_dailymkt(const char* key, int value);    // dailymkt.hip
 int csm_tune_liq(const char* key, int value);         // liquidity.hip
+int csm_tune_range(const char* key, int value);       // range.hip
 }
 // The fused month-end + scan launch behind every csm_signal* entry point and csm_pipeline
 // (signal.hip): k_signal_tail or k_signal for the panel's width and alignment and the signal

@@ -12,6 +12,7 @@ Reference mapping (file:line):
 from __future__ import annotations
 
 import ctypes
+import math
 from dataclasses import dataclass
 from typing import NamedTuple
 
@@ -215,6 +216,26 @@ class LiqModelOut:
     ZRET: torch.Tensor | None = None     # share of the return days with a zero return
     ZVOL: torch.Tensor | None = None     # share of the priced days with zero volume
     NOBS: torch.Tensor | None = None     # int32, Amihud days in the window
+
+
+class RangeSums(NamedTuple):
+    """csm_range_sums (rule HL5), each [T_m][N]: a month's ranged days and pairs and its
+    Parkinson, Corwin-Schultz and Abdi-Ranaldo sums; range_model's input."""
+    NRG: torch.Tensor                    # int32, ranged days (rule HL1)
+    NPR: torch.Tensor                    # int32, pairs of ranged days (rule HL3)
+    NCS: torch.Tensor | None             # int32, pairs with a Corwin-Schultz spread
+    SPK: torch.Tensor                    # sum of the squared log ranges
+    SCS: torch.Tensor | None             # sum of the zero-floored Corwin-Schultz spreads
+    SAR: torch.Tensor | None             # sum of the Abdi-Ranaldo terms
+
+
+@dataclass
+class RangeModelOut:
+    """csm_range_model (rule HL6), each [T_m][N]; None = not asked for."""
+    PKVOL: torch.Tensor | None = None    # Parkinson (1980) daily volatility
+    CSSPR: torch.Tensor | None = None    # Corwin-Schultz (2012) high-low spread
+    ARSPR: torch.Tensor | None = None    # Abdi-Ranaldo (2017) close-high-low spread
+    NOBS: torch.Tensor | None = None     # int32, pairs in the window
 
 
 @dataclass
@@ -1249,6 +1270,60 @@ class Engine:
                    float(scale), *(_ptr(o.get(k)) for k in self.LIQ_OUTPUTS))
         return LiqModelOut(**o)
 
+    def range_sums(self, H, L, C, month_start, max_gap=1, max_month_days=None, with_cs=True,
+                   with_ar=True) -> RangeSums:
+        """csm_range_sums (rules HL1..HL5): one pass over the daily high, low and close panels
+        for each (month, asset)'s ranged days and pairs, its sum of squared log ranges and, with
+        with_cs / with_ar, its Corwin-Schultz and Abdi-Ranaldo sums."""
+        T_d, N = H.shape
+        T_m = month_start.numel() - 1
+        for t, k in ((H, "H"), (L, "L"), (C, "C")):
+            _need(t, k, torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        NRG, NPR = self.empty((T_m, N), torch.int32), self.empty((T_m, N), torch.int32)
+        NCS = self.empty((T_m, N), torch.int32) if with_cs else None
+        SPK = self.empty((T_m, N))
+        SCS = self.empty((T_m, N)) if with_cs else None
+        SAR = self.empty((T_m, N)) if with_ar else None
+        self._call("csm_range_sums", _ptr(H), _ptr(L), _ptr(C), T_d, N, _ptr(month_start), T_m,
+                   int(max_month_days), int(max_gap), _ptr(NRG), _ptr(NPR), _ptr(NCS), _ptr(SPK),
+                   _ptr(SCS), _ptr(SAR))
+        return RangeSums(NRG, NPR, NCS, SPK, SCS, SAR)
+
+    RANGE_OUTPUTS = ("PKVOL", "CSSPR", "ARSPR", "NOBS")
+
+    def range_model(self, sums: RangeSums, window=1, min_obs=None, outputs=None) -> RangeModelOut:
+        """csm_range_model (rule HL6) on range_sums' panels over `window` calendar months
+        (1..12): Parkinson's daily volatility PKVOL (portfolio's SIG), the Corwin-Schultz and
+        Abdi-Ranaldo spreads CSSPR and ARSPR, and NOBS.  min_obs counts days (default 15 *
+        window).  outputs: the RangeModelOut fields to compute (default: all the sums given
+        allow)."""
+        T_m, N = sums.SPK.shape
+        for k in ("NRG", "NPR", "NCS"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.int32, (T_m, N), self.device)
+        for k in ("SPK", "SCS", "SAR"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.float64, (T_m, N), self.device)
+        if outputs is None:
+            outputs = tuple(k for k in self.RANGE_OUTPUTS
+                            if not (k == "CSSPR" and (sums.NCS is None or sums.SCS is None))
+                            and not (k == "ARSPR" and sums.SAR is None))
+        unknown = set(outputs) - set(self.RANGE_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = 15 * window if min_obs is None else int(min_obs)
+        o = {k: self.empty((T_m, N), torch.int32 if k == "NOBS" else torch.float64)
+             for k in outputs}
+        self._call("csm_range_model", *(_ptr(t) for t in sums), T_m, N, window, min_obs,
+                   4.0 * math.log(2.0), *(_ptr(o.get(k)) for k in self.RANGE_OUTPUTS))
+        return RangeModelOut(**o)
+
     @staticmethod
     def lagged(F, lags):
         """[T][1 + lags]: column k is the series F [T] shifted down k rows, NaN in its first k
@@ -1438,7 +1513,8 @@ class Engine:
                    *(_ptr(o.get(k)) for k in self.GROUP_OUTPUTS))
         return GroupStatsOut(**o)
 
-    def _signal_panels(self, P, month_start, signal, J, skip, n_bins, window, min_obs, V=None):
+    def _signal_panels(self, P, month_start, signal, J, skip, n_bins, window, min_obs, V=None,
+                       HLC=None):
         """(PM, S, NR) of a signal name: "mom" as run builds it, the others as run_signal does."""
         if signal == "mom":
             PM, _ = self.month_end(P, month_start)
@@ -1448,22 +1524,25 @@ class Engine:
             else:
                 _, S, NR = self.momentum(PM, J, skip)
         else:
-            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs, V=V)
+            r = self.run_signal(P, month_start, signal, J, skip, n_bins, window, min_obs, V=V,
+                                HLC=HLC)
             PM, S, NR = r.PM, r.M, r.NR
         return PM, S, NR
 
     def run_neutral(self, P, month_start, GID, n_groups, signal="mom", adjust=None, J=12, skip=1,
-                    n_bins=10, min_group=1, window=12, min_obs=None, V=None) -> PipelineOut:
+                    n_bins=10, min_group=1, window=12, min_obs=None, V=None,
+                    HLC=None) -> PipelineOut:
         """One full pass ranked inside groups (Moskowitz-Grinblatt 1999).  The signal is built as
         run (signal "mom") or run_signal (its names) build it.  adjust None: labels by
         deciles_within, the decile means pooled over the groups.  adjust "demean" / "zscore": the
         signal minus its group's mean (over its deviation), rule N5, then a plain deciles on it.
         M is the signal ranked and NR the signal's next return (rule N6).  V: the daily volume
-        panel, for run_signal's liquidity names."""
+        panel, for run_signal's liquidity names; HLC: the daily high, low and close panels, for its
+        range names."""
         if adjust not in (None, "demean", "zscore"):
             raise ValueError(f"adjust must be None, 'demean' or 'zscore', got {adjust!r}")
         PM, S, NR = self._signal_panels(P, month_start, signal, J, skip, n_bins, window, min_obs,
-                                        V)
+                                        V, HLC)
         if adjust is None:
             L, EW, CNT, NV = self.deciles_within(S, NR, GID, n_groups, n_bins, min_group,
                                                  with_nv=True)
@@ -1903,7 +1982,9 @@ class Engine:
     MARKET_SIGNALS = {"resid_mom": "RESMOM", "beta": "BETA", "ivol": "IVOL"}
     DAILY_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL", "dskew": "DSKEW", "max": "DMAX"}
     LIQ_SIGNALS = {"illiq": "ILLIQ", "dvol": "DVOL", "zret": "ZRET"}
-    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS, *LIQ_SIGNALS)
+    RANGE_SIGNALS = {"pkvol": "PKVOL", "cs_spread": "CSSPR", "ar_spread": "ARSPR"}
+    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS, *RANGE_SIGNALS,
+                   *LIQ_SIGNALS)
 
     def daily_signals(self, P, month_start, names, window=None, min_obs=None, max_gap=10):
         """{name: [T_m][N]} for names of DAILY_SIGNALS (rules V1..V4): the daily market, one pass
@@ -1935,10 +2016,20 @@ class Engine:
                             outputs=tuple(self.LIQ_SIGNALS[n] for n in names))
         return {n: getattr(lm, self.LIQ_SIGNALS[n]) for n in names}
 
+    def range_signals(self, H, L, C, month_start, names, window=None, min_obs=None, max_gap=1):
+        """{name: [T_m][N]} for names of RANGE_SIGNALS (rules HL1..HL6): one pass over the three
+        panels for the month sums and one model call.  window None: 1 month; min_obs counts days
+        (default 15 * window)."""
+        sums = self.range_sums(H, L, C, month_start, max_gap, with_cs="cs_spread" in names,
+                               with_ar="ar_spread" in names)
+        rm = self.range_model(sums, 1 if window is None else int(window), min_obs,
+                              outputs=tuple(self.RANGE_SIGNALS[n] for n in names))
+        return {n: getattr(rm, self.RANGE_SIGNALS[n]) for n in names}
+
     DAILY_FACTOR_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL"}   # the daily signals factors= serves
 
     def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
-                   min_obs=None, factors=None, V=None) -> PipelineOut:
+                   min_obs=None, factors=None, V=None, HLC=None) -> PipelineOut:
         """One full pass ranked on a signal of the daily panel: "high52", the month-end price
         over the highest daily price of the last `window` months (no momentum scan), or
         "mom_vol", mom_J over the realised daily volatility of the last `window` months.
@@ -1958,13 +2049,22 @@ class Engine:
         defaults to factor_model's / daily_fmodel's.  Any other signal with factors raises.
         Or on a liquidity signal of the daily prices and the daily volume panel V [T_d][N] (rules
         Q1..Q6): "illiq", "dvol" or "zret" over `window` months, min_obs counting days (default
-        15 * window).  These three need V; V with factors raises."""
+        15 * window).  These three need V; V with factors raises.
+        Or on a range signal of the daily high, low and close panels HLC = (H, L, C), each
+        [T_d][N] (rules HL1..HL6): "pkvol", "cs_spread" or "ar_spread".  For these a `window`
+        left at its default means 1 month, min_obs counts days (default 15 * window), and NR is
+        the next return of P's month-end prices.  These three need HLC; HLC with V or factors
+        raises."""
         if signal not in self.RUN_SIGNALS:
             raise ValueError(f"signal must be one of {self.RUN_SIGNALS}, got {signal!r}")
         if signal in self.LIQ_SIGNALS and V is None:
             raise ValueError(f"signal {signal!r} needs the daily volume panel V")
         if V is not None and factors is not None:
             raise ValueError("V and factors do not go together")
+        if signal in self.RANGE_SIGNALS and HLC is None:
+            raise ValueError(f"signal {signal!r} needs the daily panels HLC = (H, L, C)")
+        if HLC is not None and (V is not None or factors is not None):
+            raise ValueError("HLC does not go with V or factors")
         if factors is not None and signal not in (*self.MARKET_SIGNALS,
                                                   *self.DAILY_FACTOR_SIGNALS):
             raise ValueError(f"factors go with {(*self.MARKET_SIGNALS, *self.DAILY_FACTOR_SIGNALS)}"
@@ -1991,6 +2091,10 @@ class Engine:
             NR = self.next_ret(st.PM, S)
         elif signal in self.LIQ_SIGNALS:
             S = self.liq_signals(P, V, month_start, (signal,), window, min_obs)[signal]
+            NR = self.next_ret(st.PM, S)
+        elif signal in self.RANGE_SIGNALS:
+            S = self.range_signals(*HLC, month_start, (signal,), None if window == 12 else window,
+                                   min_obs)[signal]
             NR = self.next_ret(st.PM, S)
         elif signal in self.MARKET_SIGNALS:
             field = self.MARKET_SIGNALS[signal]

@@ -14,7 +14,7 @@ import pandas as pd
 import torch
 
 from .engine import Engine
-from .panel import MONTHLY_COLUMNS, DensePanel, from_long, monthly_frame
+from .panel import MONTHLY_COLUMNS, DensePanel, from_long, monthly_frame, range_from_long
 
 _ENGINES: dict[int, Engine] = {}
 
@@ -35,6 +35,12 @@ def upload_panel(panel: DensePanel, eng: Engine, with_volume: bool = True):
     V = torch.from_numpy(np.ascontiguousarray(panel.V)).to(dev) if with_volume else None
     ms = torch.from_numpy(panel.month_start.astype(np.int64)).to(dev)
     return P, V, ms
+
+
+def upload_range(daily_df, panel: DensePanel, eng: Engine):
+    """(H, L, C) of panel.range_from_long on the engine's device."""
+    return tuple(torch.from_numpy(np.ascontiguousarray(x)).to(eng.device)
+                 for x in range_from_long(daily_df, panel))
 
 
 def monthly_signal(daily_df, lookback_months=12, skip_months=1, device=None):

@@ -11,7 +11,7 @@ import numpy as np
 import pandas as pd
 
 from .engine import Engine
-from .features import get_engine, upload_panel
+from .features import get_engine, upload_panel, upload_range
 from .panel import from_long
 from .regress import build_signals
 
@@ -49,7 +49,9 @@ def information_coefficient(daily_df, signals=("mom", "high52", "beta", "ivol"),
         return None
     eng = get_engine(device)
     P, V, ms = upload_panel(panel, eng, with_volume=any(n in Engine.LIQ_SIGNALS for n in names))
-    S, X = build_signals(eng, P, ms, names, J, skip, window, V=V)
+    HLC = upload_range(daily_df, panel, eng) if any(n in Engine.RANGE_SIGNALS
+                                                    for n in names) else None
+    S, X = build_signals(eng, P, ms, names, J, skip, window, V=V, HLC=HLC)
     idx = pd.DatetimeIndex(panel.month_end, name="date")
     cols, ric, pic, nobs, rows = [], [], [], [], []
     used = 0

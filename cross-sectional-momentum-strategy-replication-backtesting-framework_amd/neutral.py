@@ -10,7 +10,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from .features import get_engine, upload_panel
+from .features import get_engine, upload_panel, upload_range
 from .panel import from_long
 from .utils import sharpe
 
@@ -60,11 +60,12 @@ def neutral_momentum(daily_df, groups, J=12, skip=1, n_bins=10, K=1, min_group=N
         raise ValueError("no ticker of the frame has a group")
     eng = get_engine(device)
     P, V, ms = upload_panel(panel, eng, with_volume=signal in eng.LIQ_SIGNALS)
+    HLC = upload_range(daily_df, panel, eng) if signal in eng.RANGE_SIGNALS else None
     GID = torch.from_numpy(gid).to(eng.device)
     G = len(names)
     mg = int(n_bins) if min_group is None else int(min_group)
     out = eng.run_neutral(P, ms, GID, G, signal=signal, adjust=adjust, J=J, skip=skip,
-                          n_bins=n_bins, min_group=mg, V=V)
+                          n_bins=n_bins, min_group=mg, V=V, HLC=HLC)
     EW, LS = out.EW, out.LS
     if K > 1:
         pf = eng.portfolio(out.L, out.NR, n_bins, K=K, with_costs=False)

@@ -116,6 +116,41 @@ def from_long(daily_df: pd.DataFrame) -> DensePanel:
                       np.asarray(tickers, dtype=object), ms, mend)
 
 
+def range_from_long(daily_df: pd.DataFrame, panel: DensePanel):
+    """The daily frame's raw `high`, `low` and `close` columns as dense (H, L, C) arrays aligned
+    to panel.days / panel.tickers (panel = from_long(daily_df)): ABSENT where the ticker has no
+    row that day, NaN where the value is missing or not numeric, and of duplicate rows the last
+    non-NaN value in row order (from_long's price rule).  ValueError when a column is missing."""
+    cols = []
+    for name in ("high", "low", "close"):
+        src = daily_df.get(name, daily_df.get(name.capitalize(), None))
+        if src is None:
+            raise ValueError(f"range_from_long: the daily frame has no {name!r} column")
+        cols.append(pd.to_numeric(src, errors="coerce"))
+    date = pd.to_datetime(daily_df.get("date", daily_df.get("Date", None)), errors="coerce")
+    date = pd.Series(date, index=daily_df.index)
+    keep = date.notna().to_numpy()
+    T_d, N = len(panel.days), len(panel.tickers)
+    dcode = panel.days.get_indexer(pd.DatetimeIndex(date.to_numpy()[keep]).normalize())
+    tcode = pd.Index(panel.tickers).get_indexer(
+        pd.Series(daily_df["ticker"].to_numpy()[keep], dtype=object))
+    if (dcode < 0).any() or (tcode < 0).any():
+        raise ValueError("range_from_long: the frame has rows outside the panel's days or tickers")
+    flat = dcode.astype(np.int64) * N + tcode
+    dup = len(np.unique(flat)) != len(flat)
+    out = []
+    for col in cols:
+        val = col.to_numpy(dtype=np.float64)[keep]
+        X = np.full(T_d * N, ABSENT_BITS, dtype=np.uint64).view(np.float64)
+        if dup:   # last non-NaN per cell in row order (NaN when the cell has none)
+            last = pd.DataFrame({"c": flat, "x": val}).groupby("c", sort=False)["x"].last()
+            X[last.index.to_numpy()] = last.to_numpy()
+        else:
+            X[flat] = val
+        out.append(X.reshape(T_d, N))
+    return tuple(out)
+
+
 def monthly_frame(panel: DensePanel, PM: np.ndarray, VOL: np.ndarray, R: np.ndarray,
                   M: np.ndarray) -> pd.DataFrame:
     """The reference's monthly output (features.py:55): one row per present (ticker, month),

@@ -11,7 +11,7 @@ import pandas as pd
 import torch
 
 from .engine import Engine
-from .features import get_engine, upload_panel
+from .features import get_engine, upload_panel, upload_range
 from .panel import from_long
 
 SIGNAL_NAMES = ("mom", "rev", *Engine.RUN_SIGNALS)
@@ -27,18 +27,24 @@ class FamaMacBethResult:
     lags: int
 
 
-def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None, V=None):
+def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None, V=None,
+                  HLC=None):
     """The named signals of a daily panel on the device, each [T_m][N], with the B1 month return
     X: "mom" (mom_J), "rev" (the month's own return) and Engine.RUN_SIGNALS' names, built by the
     calls run_signal makes.  window None: 12 months for "high52" / "mom_vol" and "dbeta", 36 for
     the monthly market model's, 1 for "divol", "dskew" and "max", 12 for the liquidity names
-    "illiq", "dvol" and "zret", which need the daily volume panel V [T_d][N]."""
+    "illiq", "dvol" and "zret", which need the daily volume panel V [T_d][N], and 1 for the range
+    names "pkvol", "cs_spread" and "ar_spread", which need the daily high, low and close panels
+    HLC = (H, L, C)."""
     unknown = [n for n in names if n not in SIGNAL_NAMES]
     if unknown:
         raise ValueError(f"signals must be among {SIGNAL_NAMES}, got {unknown}")
     liq = [n for n in names if n in Engine.LIQ_SIGNALS]
     if liq and V is None:
         raise ValueError(f"signals {liq} need the daily volume panel V")
+    rng = [n for n in names if n in Engine.RANGE_SIGNALS]
+    if rng and HLC is None:
+        raise ValueError(f"signals {rng} need the daily panels HLC = (H, L, C)")
     st = eng.month_stats(P, month_start)
     _, _, X = eng.market_factor(st.PM, with_x=True)
     out = {}
@@ -66,6 +72,8 @@ def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None,
         out.update(eng.daily_signals(P, month_start, dsig, window))
     if liq:
         out.update(eng.liq_signals(P, V, month_start, liq, window))
+    if rng:
+        out.update(eng.range_signals(*HLC, month_start, rng, window))
     return [out[n] for n in names], X
 
 
@@ -85,7 +93,9 @@ def fama_macbeth(daily_df, signals=("mom", "high52", "beta", "ivol"), J=12, skip
         return None
     eng = get_engine(device)
     P, V, ms = upload_panel(panel, eng, with_volume=any(n in Engine.LIQ_SIGNALS for n in names))
-    S, X = build_signals(eng, P, ms, names, J, skip, window, V=V)
+    HLC = upload_range(daily_df, panel, eng) if any(n in Engine.RANGE_SIGNALS
+                                                    for n in names) else None
+    S, X = build_signals(eng, P, ms, names, J, skip, window, V=V, HLC=HLC)
     if transform == "rank":
         S = [eng.xs_rank(s, pct=True) for s in S]
     Y = torch.cat([X[1:], torch.full_like(X[:1], float("nan"))])

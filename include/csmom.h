@@ -89,7 +89,9 @@ int csm_abi_version(void);
  * csm_daily_fmodel's month chunks: 0 auto | n >= 1 that many, clamped to T_m; the same bits),
  * "lsums_chunks" / "lmodel_chunks" (csm_liq_sums's and csm_liq_model's month chunks: 0 auto |
  * n >= 1 that many, clamped to T_m), "lsums_pair" (csm_liq_sums: 0 one asset per lane | 1 two
- * where the panels allow; the same bits from all three).
+ * where the panels allow; the same bits from all three), "rsums_chunks" / "rmodel_chunks"
+ * (csm_range_sums's and csm_range_model's month chunks: 0 auto | n >= 1 that many, clamped to
+ * T_m; the same bits).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -931,6 +933,64 @@ int csm_liq_model(csm_ctx* ctx, const int32_t* NP, const int32_t* ND, const int3
                   const double* SIL, const double* SH, int32_t T_m, int64_t N, int32_t Wm,
                   int32_t min_obs, double scale, double* ILLIQ, double* DVOL, double* TURN,
                   double* ZRET, double* ZVOL, int32_t* NOBS);
+
+/*
+ * Range-based signals from the daily high, low and close panels (rules HL1..HL6 in DESIGN.md
+ * section 7; no reference counterpart): Parkinson's (1980) range volatility, Corwin and Schultz's
+ * (2012) high-low bid-ask spread, zero-floored per pair, and Abdi and Ranaldo's (2017)
+ * close-high-low spread.  fp64 without contraction, every sum sequential in day (then month) order
+ * from 0.0, so two calls, and every launch shape, give the same bits.  log and exp are the device
+ * library's (OCML), so the sums are not bit-comparable with another libm's.
+ *
+ * HL1: H, L, C [T_d][N], raw (unadjusted) prices on one scale.  Row d of asset a is ranged iff
+ * H, L, C are all not NaN (the ABSENT payload counts as NaN), L > 0, H >= L and L <= C <= H; any
+ * other row is skipped and changes no state.  +-inf prices are out of contract.
+ * HL2: h = log(H), l = log(L), c = log(C), u = h - l, eta = (h + l) * 0.5.
+ * HL3: d' = the asset's previous ranged row; (d', d) is a pair iff d - d' <= max_gap (panel rows,
+ * max_gap in [1, 32]), booked in the month that holds d; never month-bounded.
+ * HL4, per pair: s = L_d > C_d' ? L_d - C_d' : (H_d < C_d' ? H_d - C_d' : 0.0); H* = H_d - s,
+ * L* = L_d - s, h* = log(H*), l* = log(L*); beta = u_d' u_d' + (h* - l*)(h* - l*);
+ * hh = H_d' >= H* ? h_d' : h*, ll = L_d' <= L* ? l_d' : l*, gamma = (hh - ll)(hh - ll);
+ * k = 3.0 - 2.0 sqrt(2.0); alpha = (sqrt(2.0 beta) - sqrt(beta)) / k - sqrt(gamma / k);
+ * e = exp(alpha); S = 2.0 (e - 1.0) / (1.0 + e).  A NaN S (L* <= 0) contributes nothing.
+ *
+ * csm_range_sums (HL5): per (month t, asset), over the days d of [month_start[t], month_start[t+1])
+ * in day order from 0:
+ *   ranged day:            NRG += 1, SPK += u * u
+ *   pair:                  NPR += 1, SAR += (c_d' - eta_d') * (c_d' - eta_d)
+ *   pair with S not NaN:   NCS += 1, SCS += S < 0 ? 0.0 : S
+ *   NRG, NPR [T_m][N] int32 out; SPK [T_m][N] out; NCS [T_m][N] int32 and SCS [T_m][N] nullable
+ *   out, together (without them no pair's two logs, exp and three square roots are computed); SAR
+ *   [T_m][N] nullable out.  A month without a day gives zeros.
+ *   max_month_days in [1, 32], csm_month_stats's bound
+ * Any N >= 1, one asset per lane.  "rsums_chunks" (csm_tune: 0 auto | n >= 1 month chunks, clamped
+ * to T_m) only changes how many workgroups there are.  No row before month_start[0] - max_gap
+ * (clipped to 0) and none at or past month_start[T_m] is read.
+ *
+ * csm_range_model (HL6) over the Wm calendar months j = t-Wm+1 .. t (t-Wm+1 >= 0): each HL5 value
+ * added over j oldest first from zero into nrg, npr, ncs, spk, scs, sar; counts enter the
+ * arithmetic as (double):
+ *   PKVOL = sqrt(spk / (c4 * nrg)): defined iff nrg >= min_obs; the daily volatility, c4 = 4 ln 2
+ *           from the caller (finite and positive)
+ *   CSSPR = scs / ncs: defined iff ncs >= min_obs
+ *   ARSPR = m > 0 ? 2.0 * sqrt(m) : 0.0, m = sar / npr: defined iff npr >= min_obs
+ *   NOBS  = npr (int32; 0 before the first whole window)
+ *   1 <= Wm <= 12;  min_obs >= 1 (days);  T_m >= 1;  any N >= 1
+ *   PKVOL, CSSPR, ARSPR [T_m][N] out, NOBS [T_m][N] int32 out: NaN where not defined; every one
+ *       nullable, at least one given; CSSPR needs NCS and SCS and ARSPR needs SAR (nullable inputs
+ *       otherwise)
+ * "rmodel_chunks" (csm_tune: 0 auto, one month per chunk | n >= 1 that many, clamped to T_m) only
+ * changes how many workgroups there are; only the panels a requested output depends on are read.
+ * The next return of any of these signals is csm_next_ret's.
+ */
+int csm_range_sums(csm_ctx* ctx, const double* H, const double* L, const double* C, int64_t T_d,
+                   int64_t N, const int64_t* month_start, int32_t T_m, int32_t max_month_days,
+                   int32_t max_gap, int32_t* NRG, int32_t* NPR, int32_t* NCS, double* SPK,
+                   double* SCS, double* SAR);
+int csm_range_model(csm_ctx* ctx, const int32_t* NRG, const int32_t* NPR, const int32_t* NCS,
+                    const double* SPK, const double* SCS, const double* SAR, int32_t T_m, int64_t N,
+                    int32_t Wm, int32_t min_obs, double c4, double* PKVOL, double* CSSPR,
+                    double* ARSPR, int32_t* NOBS);
 
 /*
  * Fama-MacBeth (1973) cross-sectional regressions (rules R1..R6 in DESIGN.md section 7; the
