@@ -16,14 +16,13 @@
 //                     from 0.0, then the slices from 0.0.  The order is a function of N alone; the
 //                     chunk length (csm_tune "dmkt_chunk_days") only decides how many workgroups
 //                     there are.
-//   k_daily_sums      V3.  k_month_stats's shape (daytrip.h): (slice of assets, one or two per
-//                     lane) x (chunk of consecutive months), the same lead-in, FD[d] a uniform
-//                     load, a month's sums flushed as the walk passes its end.  No barrier, no LDS,
-//                     no state in memory (csm_tune "dsums_chunks").
-//   k_daily_fsums     MF6.  k_daily_sums's walk on KF factors (a template on KF = 1..4): a day
-//                     row's KF factor values and their pair products are uniform, computed once
-//                     per row; two assets per lane up to DF_PAIR_MAXKF factors, one past it
-//                     (csm_tune "dfsums_chunks").
+//   k_daily_sums      V3.  The month walk of daytrip.h, one or two assets per lane: k_daily_market's
+//                     lead-in at each chunk's start, FD[d] a uniform load (csm_tune
+//                     "dsums_chunks").
+//   k_daily_fsums     MF6.  The same on KF factors (a template on KF = 1..4): a day row's KF factor
+//                     values and their pair products are uniform, computed once per row; two
+//                     assets per lane up to DF_PAIR_MAXKF factors, one past it (csm_tune
+//                     "dfsums_chunks").
 //   k_daily_fmodel    MF7.  k_daily_model's shape on the MF6 panels; fsolve.h solves each
 //                     window's normal equations (csm_tune "dfmodel_chunks").
 //   k_daily_model     V4.  A lane per asset over (64 assets) x (chunk of consecutive months); every
@@ -58,7 +57,7 @@
 #define DF_PAIR_MAXKF 2
 
 // "dmkt_chunk_days": day rows per chunk of k_daily_market, 0 auto (dm_auto_chunk_days) | n >= 1
-// "dsums_chunks":    month chunks of k_daily_sums, 0 auto (ds_auto_chunks) | n >= 1 that many
+// "dsums_chunks":    month chunks of k_daily_sums, 0 auto (scan.h auto_chunks) | n >= 1 that many
 // "dmodel_chunks":   month chunks of k_daily_model, 0 auto, one month per chunk | n >= 1 that many
 // (both clamped to T_m).  Every value gives the same bits.
 // "dfsums_chunks" / "dfmodel_chunks": the same two for k_daily_fsums and k_daily_fmodel.
@@ -244,72 +243,51 @@ __device__ __forceinline__ void ds_fload(double (&f)[MS_TRIP], const double* __r
   for (int i = 0; i < MS_TRIP; ++i) f[i] = d + i < dB ? FD[d + i] : qnan();
 }
 
+// k_daily_sums's walker (daytrip.h): the V1 lead-in, P's rows and FD's, which are uniform.
+template <int VEC>
+struct DsWalker {
+  const double* __restrict__ P;
+  const double* __restrict__ FD;
+  int64_t N, a;
+  int max_gap;
+  DsOut out;
+  DrLane lane[VEC];
+  DsAcc acc[VEC];
+  struct Rows {
+    double x[MS_TRIP][VEC], f[MS_TRIP];
+  };
+
+  __device__ __forceinline__ void reset() {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) ds_reset(acc[k]);
+  }
+  __device__ __forceinline__ void begin(int64_t dA) {
+    dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
+    reset();
+  }
+  __device__ __forceinline__ void load(Rows& r, int64_t d, int64_t dB) const {
+    trip_load<MS_TRIP, VEC>(r.x, P, N, a, d, dB, absent_val());
+    ds_fload(r.f, FD, d, dB);
+  }
+  __device__ __forceinline__ void own(Rows&, int64_t, int64_t) const {}
+  __device__ __forceinline__ void step(const Rows& r, int i) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) ds_step(acc[k], lane[k], r.x[i][k], r.f[i], max_gap);
+  }
+  __device__ __forceinline__ void flush(int m) {   // the V1 state runs on
+    ds_flush<VEC>(acc, (int64_t)m * N + a, out);
+    reset();
+  }
+};
+
 template <int VEC>
 __global__ __launch_bounds__(MS_THREADS) void k_daily_sums(
     const double* __restrict__ P, const double* __restrict__ FD, int64_t T_d, int64_t N,
     const int64_t* __restrict__ ms, int T_m, int G, int max_gap, DsOut out) {
   const int64_t a = ((int64_t)blockIdx.x * MS_THREADS + threadIdx.x) * VEC;
   if (a >= N) return;   // (no barrier anywhere below)
-  int m0, m1;
-  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
-  // the chunk's day rows and month ends, clipped as k_month_stats clips them
-  const int64_t dA = ms_clip(ms[m0], 0, T_d), dB = ms_clip(ms[m1], dA, T_d);
-  int m = m0;
-  int64_t nb = ms_clip(ms[m0 + 1], dA, dB);   // end of month m
-  DrLane lane[VEC];
-  dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
-  DsAcc acc[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) ds_reset(acc[k]);
-  auto next_month = [&]() {   // (uniform) month m is complete; the V1 state runs on
-    ds_flush<VEC>(acc, (int64_t)m * N + a, out);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) ds_reset(acc[k]);
-    ++m;
-    nb = m < m1 ? ms_clip(ms[m + 1], dA, dB) : dB;
-  };
-  double cur[MS_TRIP][VEC], nxt[MS_TRIP][VEC], fc[MS_TRIP], fn[MS_TRIP];
-  ms_load<VEC>(cur, P, N, a, dA, dB);
-  ds_fload(fc, FD, dA, dB);
-  for (int64_t d = dA; d < dB; d += MS_TRIP) {
-    ms_load<VEC>(nxt, P, N, a, d + MS_TRIP, dB);
-    ds_fload(fn, FD, d + MS_TRIP, dB);
-    if (d + MS_TRIP <= nb) {   // (uniform) the trip lies inside month m: one straight block
-#pragma unroll
-      for (int i = 0; i < MS_TRIP; ++i) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) ds_step(acc[k], lane[k], cur[i][k], fc[i], max_gap);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < MS_TRIP; ++i) {
-        while (m < m1 && d + i >= nb) next_month();   // (zero-length months: several)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) ds_step(acc[k], lane[k], cur[i][k], fc[i], max_gap);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MS_TRIP; ++i) {
-      fc[i] = fn[i];
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) cur[i][k] = nxt[i][k];
-    }
-  }
-  while (m < m1) next_month();   // the last month, and whatever zero-length months follow it
-}
-
-// Auto chunk count: about eight (slice, chunk) workgroups per CU and no chunk shorter than three
-// months.  Unlike k_month_stats, whose finest chunking is its fastest, a chunk here pays a lead-in
-// (a dependent row load before its first trip) and fills a deeper pipeline (192 VGPRs with two
-// assets per lane, two waves per SIMD).  MI355X (profiles/r14/bench_dailymkt_sweep.log):
-// 100,000 assets x 461 months 1 / 11 / 88 / 461 chunks 3.94 / 2.37 / 2.55 / 3.62 ms (auto 11);
-// 5,000 assets x 300 months 1 / 13 / 103 / 300 chunks 2.17 / 0.212 / 0.128 / 0.160 ms (auto 100)
-static inline int ds_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
-  const int64_t want = (int64_t)8 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-  int64_t G = (want + slices - 1) / slices;
-  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
-  if (G > most) G = most;
-  return (int)G;
+  DsWalker<VEC> w{P, FD, N, a, max_gap, out};
+  month_walk<MS_TRIP>(w, ms, T_m, G, T_d);
 }
 
 // ------------------------------------------------------------------------------- MF6
@@ -420,86 +398,57 @@ __device__ __forceinline__ void df_fload(double (&f)[MS_TRIP][KF], const double*
   }
 }
 
-// k_daily_sums's walk on KF factors.
+// k_daily_fsums's walker (daytrip.h): k_daily_sums's on KF factors.  Up to DF_PAIR_MAXKF factors
+// the factor rows are loaded a trip ahead with the prices; past it a trip loads its own.
+template <int KF, int VEC>
+struct DfWalker {
+  static constexpr bool AHEAD = KF <= DF_PAIR_MAXKF;
+  const double* __restrict__ P;
+  const double* __restrict__ FD;
+  int64_t N, a, plane;   // plane: T_m * N
+  int max_gap;
+  DfOut out;
+  DrLane lane[VEC];
+  DfAcc<KF> acc[VEC];
+  struct Rows {
+    double x[MS_TRIP][VEC];
+    double f[MS_TRIP][KF] = {};   // (own() writes them when load() does not)
+  };
+
+  __device__ __forceinline__ void reset() {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) df_reset<KF>(acc[k]);
+  }
+  __device__ __forceinline__ void begin(int64_t dA) {
+    dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
+    reset();
+  }
+  __device__ __forceinline__ void load(Rows& r, int64_t d, int64_t dB) const {
+    trip_load<MS_TRIP, VEC>(r.x, P, N, a, d, dB, absent_val());
+    if (AHEAD) df_fload<KF>(r.f, FD, d, dB);
+  }
+  __device__ __forceinline__ void own(Rows& r, int64_t d, int64_t dB) const {
+    if (!AHEAD) df_fload<KF>(r.f, FD, d, dB);
+  }
+  __device__ __forceinline__ void step(const Rows& r, int i) {
+    const DfRow<KF> w = df_row<KF>(r.f[i]);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) df_step<KF>(acc[k], lane[k], r.x[i][k], w, max_gap);
+  }
+  __device__ __forceinline__ void flush(int m) {   // the V1 state runs on
+    df_flush<KF, VEC>(acc, (int64_t)m * N + a, plane, out);
+    reset();
+  }
+};
+
 template <int KF, int VEC>
 __global__ __launch_bounds__(MS_THREADS) void k_daily_fsums(
     const double* __restrict__ P, const double* __restrict__ FD, int64_t T_d, int64_t N,
     const int64_t* __restrict__ ms, int T_m, int G, int max_gap, DfOut out) {
   const int64_t a = ((int64_t)blockIdx.x * MS_THREADS + threadIdx.x) * VEC;
   if (a >= N) return;   // (no barrier anywhere below)
-  int m0, m1;
-  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
-  const int64_t dA = ms_clip(ms[m0], 0, T_d), dB = ms_clip(ms[m1], dA, T_d);
-  const int64_t plane = (int64_t)T_m * N;
-  int m = m0;
-  int64_t nb = ms_clip(ms[m0 + 1], dA, dB);   // end of month m
-  DrLane lane[VEC];
-  dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
-  DfAcc<KF> acc[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) df_reset<KF>(acc[k]);
-  auto next_month = [&]() {   // (uniform) month m is complete; the V1 state runs on
-    df_flush<KF, VEC>(acc, (int64_t)m * N + a, plane, out);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) df_reset<KF>(acc[k]);
-    ++m;
-    nb = m < m1 ? ms_clip(ms[m + 1], dA, dB) : dB;
-  };
-  // the next trip's factor rows are loaded a trip ahead up to DF_PAIR_MAXKF factors; past it a
-  // trip loads its own rows
-  constexpr bool PF = KF <= DF_PAIR_MAXKF;
-  double cur[MS_TRIP][VEC], nxt[MS_TRIP][VEC], fc[MS_TRIP][KF], fn[MS_TRIP][KF];
-  ms_load<VEC>(cur, P, N, a, dA, dB);
-  if (PF) df_fload<KF>(fc, FD, dA, dB);
-  for (int64_t d = dA; d < dB; d += MS_TRIP) {
-    ms_load<VEC>(nxt, P, N, a, d + MS_TRIP, dB);
-    if (PF)
-      df_fload<KF>(fn, FD, d + MS_TRIP, dB);
-    else
-      df_fload<KF>(fc, FD, d, dB);
-    if (d + MS_TRIP <= nb) {   // (uniform) the trip lies inside month m: one straight block
-#pragma unroll
-      for (int i = 0; i < MS_TRIP; ++i) {
-        const DfRow<KF> w = df_row<KF>(fc[i]);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) df_step<KF>(acc[k], lane[k], cur[i][k], w, max_gap);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < MS_TRIP; ++i) {
-        while (m < m1 && d + i >= nb) next_month();   // (zero-length months: several)
-        const DfRow<KF> w = df_row<KF>(fc[i]);
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) df_step<KF>(acc[k], lane[k], cur[i][k], w, max_gap);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MS_TRIP; ++i) {
-      if (PF) {
-#pragma unroll
-        for (int c = 0; c < KF; ++c) fc[i][c] = fn[i][c];
-      }
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) cur[i][k] = nxt[i][k];
-    }
-  }
-  while (m < m1) next_month();   // the last month, and whatever zero-length months follow it
-}
-
-// Auto chunk count of k_daily_fsums: ds_auto_chunks' rule with about 32 (slice, chunk) workgroups
-// per CU in place of eight: the deeper accumulator set leaves a CU fewer resident waves, and more,
-// shorter chunks even the fill out.  MI355X (profiles/r15/bench_fsums_sweep.log), KF = 1 / KF = 4:
-// 100,000 assets x 461 months 3 / 6 / 12 / 30 / 100 chunks 2.65 / 2.14 / 2.06 / 1.97 / 2.16 ms and
-// 5.26 / 5.09 / 4.65 / 4.48 / 4.61 ms (auto 42 and 21: 2.21 and 4.57 ms in bench_factor.log,
-// k_daily_sums 2.43 there; eight per CU gave 11 and 6 chunks, 2.06 and 5.00 ms in the sweep's run);
-// 5,000 assets x 300 months 3 / 6 / 12 / 30 / 100 chunks 0.703 / 0.370 / 0.207 / 0.135 / 0.114 ms
-// and 1.023 / 0.532 / 0.288 / 0.259 / 0.216 ms (auto 100)
-static inline int df_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
-  const int64_t want = (int64_t)32 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-  int64_t G = (want + slices - 1) / slices;
-  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
-  if (G > most) G = most;
-  return (int)G;
+  DfWalker<KF, VEC> w{P, FD, N, a, (int64_t)T_m * N, max_gap, out};
+  month_walk<MS_TRIP>(w, ms, T_m, G, T_d);
 }
 
 template <int KF>
@@ -751,13 +700,14 @@ int csm_daily_sums(csm_ctx* ctx, const double* P, const double* FD, int64_t T_d,
   const bool v2 = (N % 2 == 0) && aligned16(P) && aligned8(NO) && aligned16(SR) &&
                   aligned16(SF) && aligned16(SRR) && aligned16(SFF) && aligned16(SRF) &&
                   (!SR3 || aligned16(SR3)) && (!RMAX || aligned16(RMAX));
-  const int vec = v2 ? 2 : 1;
-  const int64_t slices = (N + (int64_t)MS_THREADS * vec - 1) / ((int64_t)MS_THREADS * vec);
-  int64_t G = g_tune_dsums_chunks > 0 ? g_tune_dsums_chunks : ds_auto_chunks(ctx, slices, T_m);
-  if (G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
-  const int g = (int)G;
-  const dim3 grid((unsigned)slices, (unsigned)g);
+  // Auto chunk count: about eight workgroups per CU (scan.h auto_chunks).  Unlike k_month_stats,
+  // whose finest chunking is its fastest, a chunk here pays a lead-in (a dependent row load
+  // before its first trip) and fills a deeper pipeline (two assets per lane leave a SIMD two
+  // waves).  MI355X (profiles/r14/bench_dailymkt_sweep.log): 100,000 assets x 461 months 1 / 11 /
+  // 88 / 461 chunks 3.94 / 2.37 / 2.55 / 3.62 ms (auto 11); 5,000 assets x 300 months 1 / 13 /
+  // 103 / 300 chunks 2.17 / 0.212 / 0.128 / 0.160 ms (auto 100)
+  const dim3 grid = month_grid(ctx, N, MS_THREADS * (v2 ? 2 : 1), g_tune_dsums_chunks, 8, T_m);
+  const int g = (int)grid.y;
   const DsOut out{NO, SR, SF, SRR, SFF, SRF, SR3, RMAX};
   if (v2)
     hipLaunchKernelGGL(k_daily_sums<2>, grid, dim3(MS_THREADS), 0, ctx->stream, P, FD, T_d, N,
@@ -825,13 +775,16 @@ int csm_daily_fsums(csm_ctx* ctx, const double* P, const double* FD, int64_t T_d
   const bool v2 = KF <= DF_PAIR_MAXKF && (N % 2 == 0) && aligned16(P) && aligned8(NO) &&
                   aligned16(SR) && aligned16(SRR) && aligned16(SF) && aligned16(SRF) &&
                   aligned16(SFF);
-  const int vec = v2 ? 2 : 1;
-  const int64_t slices = (N + (int64_t)MS_THREADS * vec - 1) / ((int64_t)MS_THREADS * vec);
-  int64_t G = g_tune_dfsums_chunks > 0 ? g_tune_dfsums_chunks : df_auto_chunks(ctx, slices, T_m);
-  if (G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
-  const int g = (int)G;
-  const dim3 grid((unsigned)slices, (unsigned)g);
+  // Auto chunk count: about 32 workgroups per CU in place of k_daily_sums's eight: the deeper
+  // accumulator set leaves a CU fewer resident waves, and more, shorter chunks even the fill out.
+  // MI355X (profiles/r15/bench_fsums_sweep.log), KF = 1 / KF = 4: 100,000 assets x 461 months 3 /
+  // 6 / 12 / 30 / 100 chunks 2.65 / 2.14 / 2.06 / 1.97 / 2.16 ms and 5.26 / 5.09 / 4.65 / 4.48 /
+  // 4.61 ms (auto 42 and 21: 2.21 and 4.57 ms in bench_factor.log, k_daily_sums 2.43 there; eight
+  // per CU gave 11 and 6 chunks, 2.06 and 5.00 ms in the sweep's run); 5,000 assets x 300 months
+  // 3 / 6 / 12 / 30 / 100 chunks 0.703 / 0.370 / 0.207 / 0.135 / 0.114 ms and 1.023 / 0.532 /
+  // 0.288 / 0.259 / 0.216 ms (auto 100)
+  const dim3 grid = month_grid(ctx, N, MS_THREADS * (v2 ? 2 : 1), g_tune_dfsums_chunks, 32, T_m);
+  const int g = (int)grid.y;
   const DfOut out{NO, SR, SRR, SF, SRF, SFF};
   switch (KF) {
     case 1: df_launch<1>(ctx, v2, grid, P, FD, T_d, N, month_start, T_m, g, max_gap, out); break;

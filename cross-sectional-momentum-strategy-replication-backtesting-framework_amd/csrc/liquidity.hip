@@ -3,11 +3,8 @@
 // the window model on them -- ILLIQ, dollar average daily volume, turnover, and the shares of
 // zero-return (Lesmond, Ogden and Trzcinka 1999) and zero-volume days.
 //
-//   k_liq_sums        Q2.  k_daily_sums's shape on two panels: (slice of MS_THREADS lanes, one or
-//                     two adjacent assets per lane) x (chunk of consecutive months).  The V1
-//                     lead-in walks P only; then trips of TRIP day rows of P and V, the next trip's
-//                     loads in flight, a month's values flushed as the walk passes its end.  No
-//                     barrier, no LDS, no state in memory (csm_tune "lsums_chunks").
+//   k_liq_sums        Q2.  The month walk of daytrip.h on two panels: the V1 lead-in walks P only;
+//                     then trips of TRIP day rows of P and V (csm_tune "lsums_chunks").
 //                     Two panels double k_daily_sums's trip buffers, and the registers decide the
 //                     shape.  The gfx950 compile (no scratch in any) and, on MI355X, 100,000 x
 //                     10,000 days / 5,000 x 6,522 days at each one's best chunk count
@@ -22,7 +19,9 @@
 //                     behind csm_tune "lsums_pair" for even N with aligned panels: it issues half
 //                     the load instructions and measured 2 to 5 % slower in both runs (bench_liq.log:
 //                     3.46 / 0.162 ms against 3.38 / 0.155), two waves a SIMD hiding less than
-//                     three.  The other two are not in the library.
+//                     three.  The other two are not in the library.  (On daytrip.h's month_walk
+//                     the first takes 159 VGPRs, still three waves a SIMD, and measures 0.5 to
+//                     0.8 % slower: profiles/r18/walk_speed.md.)
 //   k_liq_model       Q3.  k_daily_model's shape: a lane per asset over (64 assets) x (chunk of
 //                     consecutive months); every window's sums are added again from its oldest
 //                     month, read from the Q2 panels a requested output depends on (csm_tune
@@ -35,7 +34,7 @@
 #define LQM_THREADS 64
 #define LQM_MAXW 12
 
-// "lsums_chunks":  month chunks of k_liq_sums, 0 auto (lq_auto_chunks) | n >= 1 that many
+// "lsums_chunks":  month chunks of k_liq_sums, 0 auto (scan.h auto_chunks) | n >= 1 that many
 // "lmodel_chunks": month chunks of k_liq_model, 0 auto, one month per chunk | n >= 1 that many
 // (both clamped to T_m)
 // "lsums_pair":    0 auto, one asset per lane | 1 two per lane where the panels allow
@@ -111,36 +110,43 @@ __device__ __forceinline__ void lq_flush(const LqAcc (&s)[VEC], int64_t o, const
   }
 }
 
-// Rows [d, d + TRIP) of the lane's assets from one panel (daytrip.h ms_load at any trip length);
-// rows from dB on are NaN: unpriced days, which change nothing.
+// k_liq_sums's walker (daytrip.h): the V1 lead-in on P, then P's and V's rows; rows past the chunk
+// are NaN: unpriced days, which change nothing.
 template <int TRIP, int VEC>
-__device__ __forceinline__ void lq_load(double (&x)[TRIP][VEC], const double* __restrict__ X,
-                                        int64_t N, int64_t a, int64_t d, int64_t dB) {
-  const double* p = X + d * N + a;
-  auto row = [&](int i) {
-    if (VEC == 2) {
-      const double2 t = *reinterpret_cast<const double2*>(p + (int64_t)i * N);
-      x[i][0] = t.x;
-      x[i][VEC - 1] = t.y;
-    } else {
-      x[i][0] = p[(int64_t)i * N];
-    }
+struct LqWalker {
+  const double* __restrict__ P;
+  const double* __restrict__ V;
+  int64_t N, a;
+  int max_gap;
+  LqOut out;
+  DrLane lane[VEC];
+  LqAcc acc[VEC];
+  struct Rows {
+    double p[TRIP][VEC], v[TRIP][VEC];
   };
-  if (d + TRIP <= dB) {   // (uniform) a whole trip: no predicate on any load
+
+  __device__ __forceinline__ void reset() {
 #pragma unroll
-    for (int i = 0; i < TRIP; ++i) row(i);
-  } else {
-#pragma unroll
-    for (int i = 0; i < TRIP; ++i) {
-      if (d + i < dB) {
-        row(i);
-      } else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) x[i][k] = qnan();
-      }
-    }
+    for (int k = 0; k < VEC; ++k) lq_reset(acc[k]);
   }
-}
+  __device__ __forceinline__ void begin(int64_t dA) {
+    dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
+    reset();
+  }
+  __device__ __forceinline__ void load(Rows& r, int64_t d, int64_t dB) const {
+    trip_load<TRIP, VEC>(r.p, P, N, a, d, dB, qnan());
+    trip_load<TRIP, VEC>(r.v, V, N, a, d, dB, qnan());
+  }
+  __device__ __forceinline__ void own(Rows&, int64_t, int64_t) const {}
+  __device__ __forceinline__ void step(const Rows& r, int i) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) lq_step(acc[k], lane[k], r.p[i][k], r.v[i][k], max_gap);
+  }
+  __device__ __forceinline__ void flush(int m) {   // the V1 state runs on
+    lq_flush<VEC>(acc, (int64_t)m * N + a, out);
+    reset();
+  }
+};
 
 template <int TRIP, int VEC>
 __global__ __launch_bounds__(MS_THREADS) void k_liq_sums(
@@ -148,69 +154,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_liq_sums(
     const int64_t* __restrict__ ms, int T_m, int G, int max_gap, LqOut out) {
   const int64_t a = ((int64_t)blockIdx.x * MS_THREADS + threadIdx.x) * VEC;
   if (a >= N) return;   // (no barrier anywhere below; VEC == 2 has N even, so a + 1 < N)
-  int m0, m1;
-  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
-  // the chunk's day rows and month ends, clipped as k_daily_sums clips them
-  const int64_t dA = ms_clip(ms[m0], 0, T_d), dB = ms_clip(ms[m1], dA, T_d);
-  int m = m0;
-  int64_t nb = ms_clip(ms[m0 + 1], dA, dB);   // end of month m
-  DrLane lane[VEC];
-  dr_lead_in<VEC>(lane, P, N, dA, max_gap, [&](int k) { return a + k; });
-  LqAcc acc[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) lq_reset(acc[k]);
-  auto next_month = [&]() {   // (uniform) month m is complete; the V1 state runs on
-    lq_flush<VEC>(acc, (int64_t)m * N + a, out);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) lq_reset(acc[k]);
-    ++m;
-    nb = m < m1 ? ms_clip(ms[m + 1], dA, dB) : dB;
-  };
-  double pc[TRIP][VEC], pn[TRIP][VEC], vc[TRIP][VEC], vn[TRIP][VEC];
-  lq_load<TRIP, VEC>(pc, P, N, a, dA, dB);
-  lq_load<TRIP, VEC>(vc, V, N, a, dA, dB);
-  for (int64_t d = dA; d < dB; d += TRIP) {
-    lq_load<TRIP, VEC>(pn, P, N, a, d + TRIP, dB);
-    lq_load<TRIP, VEC>(vn, V, N, a, d + TRIP, dB);
-    if (d + TRIP <= nb) {   // (uniform) the trip lies inside month m: one straight block
-#pragma unroll
-      for (int i = 0; i < TRIP; ++i) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) lq_step(acc[k], lane[k], pc[i][k], vc[i][k], max_gap);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < TRIP; ++i) {
-        while (m < m1 && d + i >= nb) next_month();   // (zero-length months: several)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) lq_step(acc[k], lane[k], pc[i][k], vc[i][k], max_gap);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < TRIP; ++i) {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) {
-        pc[i][k] = pn[i][k];
-        vc[i][k] = vn[i][k];
-      }
-    }
-  }
-  while (m < m1) next_month();   // the last month, and whatever zero-length months follow it
-}
-
-// Auto chunk count: k_daily_fsums's rule (df_auto_chunks), about 32 (slice, chunk) workgroups per
-// CU and no chunk shorter than three months.  MI355X (profiles/r16/bench_liq_sweep.log), one asset
-// per lane, TRIP 8: 100,000 assets x 461 months 3 / 6 / 11 / 22 / 44 / 88 chunks 3.91 / 3.95 / 3.75 /
-// 3.72 / 3.69 / 3.65 ms (auto 21; eight per CU would give 6); 5,000 assets x 300 months 13 / 25 /
-// 50 / 100 / 150 / 300 chunks 0.214 / 0.147 / 0.167 / 0.158 / 0.161 / 0.180 ms (auto 100).  Two per
-// lane, TRIP 4: 5.25 / 4.10 / 3.98 / 3.80 / 3.80 / 3.76 ms and 0.295 / 0.180 / 0.154 / 0.165 /
-// 0.171 / 0.195 ms.
-static inline int lq_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
-  const int64_t want = (int64_t)32 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-  int64_t G = (want + slices - 1) / slices;
-  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
-  if (G > most) G = most;
-  return (int)G;
+  LqWalker<TRIP, VEC> w{P, V, N, a, max_gap, out};
+  month_walk<TRIP>(w, ms, T_m, G, T_d);
 }
 
 // ------------------------------------------------------------------------------- Q3
@@ -307,13 +252,14 @@ int csm_liq_sums(csm_ctx* ctx, const double* P, const double* V, int64_t T_d, in
                   aligned8(NP) && aligned8(ND) && aligned8(NA) && (!NZR || aligned8(NZR)) &&
                   (!NZV || aligned8(NZV)) && (!SV || aligned16(SV)) && aligned16(SDV) &&
                   aligned16(SIL);
-  const int vec = v2 ? 2 : 1;
-  const int64_t slices = (N + (int64_t)MS_THREADS * vec - 1) / ((int64_t)MS_THREADS * vec);
-  int64_t G = g_tune_lsums_chunks > 0 ? g_tune_lsums_chunks : lq_auto_chunks(ctx, slices, T_m);
-  if (G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
-  const int g = (int)G;
-  const dim3 grid((unsigned)slices, (unsigned)g);
+  // Auto chunk count: k_daily_fsums's, about 32 workgroups per CU (scan.h auto_chunks).  MI355X
+  // (profiles/r16/bench_liq_sweep.log), one asset per lane, TRIP 8: 100,000 assets x 461 months
+  // 3 / 6 / 11 / 22 / 44 / 88 chunks 3.91 / 3.95 / 3.75 / 3.72 / 3.69 / 3.65 ms (auto 21; eight
+  // per CU would give 6); 5,000 assets x 300 months 13 / 25 / 50 / 100 / 150 / 300 chunks 0.214 /
+  // 0.147 / 0.167 / 0.158 / 0.161 / 0.180 ms (auto 100).  Two per lane, TRIP 4: 5.25 / 4.10 /
+  // 3.98 / 3.80 / 3.80 / 3.76 ms and 0.295 / 0.180 / 0.154 / 0.165 / 0.171 / 0.195 ms.
+  const dim3 grid = month_grid(ctx, N, MS_THREADS * (v2 ? 2 : 1), g_tune_lsums_chunks, 32, T_m);
+  const int g = (int)grid.y;
   const LqOut out{NP, ND, NA, NZR, NZV, SV, SDV, SIL};
   if (v2)
     hipLaunchKernelGGL((k_liq_sums<LQ_TRIP_PAIR, 2>), grid, dim3(MS_THREADS), 0, ctx->stream, P, V,

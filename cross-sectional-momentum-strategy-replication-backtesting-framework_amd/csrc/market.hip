@@ -35,8 +35,8 @@
 #define NX_THREADS 64
 #define NX_TRIP 4        // months per trip of k_next_ret: the next trip's loads are in flight
 
-// the month chunks of k_market_model: 0 auto (mm_auto_chunks) | n >= 1 that many (clamped to T_m)
-// the month chunks of k_factor_model, the same values ("fm_chunks", fm_auto_chunks)
+// the month chunks of k_market_model: 0 auto (scan.h auto_chunks) | n >= 1 that many (clamped to
+// T_m); the month chunks of k_factor_model, the same values ("fm_chunks")
 static int g_tune_mm_chunks = 0;
 static int g_tune_fm_chunks = 0;
 static const TuneKnob g_knobs[] = {
@@ -262,23 +262,6 @@ __global__ __launch_bounds__(MM_THREADS) void k_market_model(
   }
 }
 
-// Auto chunk count: about 64 (slice, chunk) workgroups per CU, and no chunk shorter than three
-// months.  The kernel is bound by fp64 VALU issue (five walks of the window per asset-month), not
-// by bytes, and a workgroup's ring (18 KiB at Wb = 36) leaves a CU eight of them, so what the
-// chunks buy is an even fill and a short tail; past that, the Wb - 1 months a chunk warms up on
-// cost more than they return.  MI355X, Wb = 36, all outputs, before a month without f was stored
-// as a month without x (profiles/r11/bench_market_*_sweep.log; after it, 3.23 and 0.168 ms at
-// the auto counts of 11 and 100, bench_market_*.log):
-// 100,000 assets x 461 months 1 / 2 / 12 / 46 / 461 chunks 4.62 / 4.13 / 3.17 / 3.14 / 6.27 ms;
-// 5,000 assets x 300 months 1 / 8 / 30 / 100 / 300 chunks 1.76 / 0.308 / 0.185 / 0.167 / 0.212 ms
-static inline int mm_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
-  const int64_t want = (int64_t)64 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-  int64_t G = (want + slices - 1) / slices;
-  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
-  if (G > most) G = most;
-  return (int)G;
-}
-
 // ---------------------------------------------------------------------------- MF1..MF5
 struct FmOut {
   double* BETA;   // [KF][T_m][N]
@@ -475,17 +458,6 @@ __global__ __launch_bounds__(MM_THREADS) void k_factor_model(
   }
 }
 
-// Auto chunk count of k_factor_model: mm_auto_chunks' rule.  The kernel has k_market_model's
-// shape, warm-up cost and LDS footprint (plus Wb * KF doubles), and the sweep has its shape too.
-// MI355X, Wb = 36, all outputs, KF = 1 / KF = 4 (profiles/r15/bench_factor_sweep.log):
-// 100,000 assets x 461 months 2 / 11 (auto) / 12 / 46 / 150 chunks 4.52 / 3.51 / 3.55 / 3.43 /
-// 4.10 ms and 10.60 / 7.80 / 8.03 / 7.49 / 8.16 ms; 5,000 assets x 300 months 2 / 12 / 46 / 100
-// (auto) / 150 chunks 1.100 / 0.240 / 0.179 / 0.177 / 0.187 ms and 2.023 / 0.483 / 0.373 / 0.349 /
-// 0.356 ms
-static inline int fm_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
-  return mm_auto_chunks(ctx, slices, T_m);
-}
-
 template <int KF>
 static inline void fm_launch(csm_ctx* ctx, dim3 grid, const double* PM, const double* F, int T_m,
                              int64_t N, int Wb, int J, int skip, int min_obs, int G,
@@ -599,13 +571,19 @@ int csm_market_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_
     J = 2;
     skip = 0;
   }
-  const int64_t slices = (N + MM_THREADS - 1) / MM_THREADS;
-  int64_t G = g_tune_mm_chunks > 0 ? g_tune_mm_chunks : mm_auto_chunks(ctx, slices, T_m);
-  if (G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
+  // Auto chunk count: about 64 workgroups per CU (scan.h auto_chunks).  The kernel is bound by
+  // fp64 VALU issue (five walks of the window per asset-month), not by bytes, and a workgroup's
+  // ring (18 KiB at Wb = 36) leaves a CU eight of them, so what the chunks buy is an even fill and
+  // a short tail; past that, the Wb - 1 months a chunk warms up on cost more than they return.
+  // MI355X, Wb = 36, all outputs, before a month without f was stored as a month without x
+  // (profiles/r11/bench_market_*_sweep.log; after it, 3.23 and 0.168 ms at the auto counts of 11
+  // and 100, bench_market_*.log): 100,000 assets x 461 months 1 / 2 / 12 / 46 / 461 chunks 4.62 /
+  // 4.13 / 3.17 / 3.14 / 6.27 ms; 5,000 assets x 300 months 1 / 8 / 30 / 100 / 300 chunks 1.76 /
+  // 0.308 / 0.185 / 0.167 / 0.212 ms
+  const dim3 grid = month_grid(ctx, N, MM_THREADS, g_tune_mm_chunks, 64, T_m);
   const MmOut o{BETA, ALPHA, IVOL, RESMOM, NOBS};
-  hipLaunchKernelGGL(k_market_model, dim3((unsigned)slices, (unsigned)G), dim3(MM_THREADS),
-                     mm_lds_bytes(Wb), ctx->stream, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o);
+  hipLaunchKernelGGL(k_market_model, grid, dim3(MM_THREADS), mm_lds_bytes(Wb), ctx->stream, PM, F,
+                     T_m, N, Wb, J, skip, min_obs, (int)grid.y, o);
   LAUNCH_CHECK(ctx, "k_market_model");
   return CSM_OK;
 }
@@ -640,17 +618,20 @@ int csm_factor_model(csm_ctx* ctx, const double* PM, const double* F, int32_t T_
     J = 2;
     skip = 0;
   }
-  const int64_t slices = (N + MM_THREADS - 1) / MM_THREADS;
-  int64_t G = g_tune_fm_chunks > 0 ? g_tune_fm_chunks : fm_auto_chunks(ctx, slices, T_m);
-  if (G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
+  // Auto chunk count: k_market_model's.  The kernel has its shape, warm-up cost and LDS footprint
+  // (plus Wb * KF doubles), and the sweep has its shape too.  MI355X, Wb = 36, all outputs, KF = 1 /
+  // KF = 4 (profiles/r15/bench_factor_sweep.log): 100,000 assets x 461 months 2 / 11 (auto) / 12 /
+  // 46 / 150 chunks 4.52 / 3.51 / 3.55 / 3.43 / 4.10 ms and 10.60 / 7.80 / 8.03 / 7.49 / 8.16 ms;
+  // 5,000 assets x 300 months 2 / 12 / 46 / 100 (auto) / 150 chunks 1.100 / 0.240 / 0.179 /
+  // 0.177 / 0.187 ms and 2.023 / 0.483 / 0.373 / 0.349 / 0.356 ms
+  const dim3 grid = month_grid(ctx, N, MM_THREADS, g_tune_fm_chunks, 64, T_m);
+  const int G = (int)grid.y;
   const FmOut o{BETA, ALPHA, IVOL, RESMOM, R2, NOBS};
-  const dim3 grid((unsigned)slices, (unsigned)G);
   switch (KF) {
-    case 1: fm_launch<1>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
-    case 2: fm_launch<2>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
-    case 3: fm_launch<3>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
-    default: fm_launch<4>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, (int)G, o); break;
+    case 1: fm_launch<1>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, G, o); break;
+    case 2: fm_launch<2>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, G, o); break;
+    case 3: fm_launch<3>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, G, o); break;
+    default: fm_launch<4>(ctx, grid, PM, F, T_m, N, Wb, J, skip, min_obs, G, o); break;
   }
   LAUNCH_CHECK(ctx, "k_factor_model");
   return CSM_OK;

@@ -3,12 +3,10 @@
 // Corwin-Schultz (2012) two-day high-low spreads and of Abdi-Ranaldo (2017) close-high-low terms,
 // and the window model on them -- Parkinson volatility and the two bid-ask spread estimates.
 //
-//   k_range_sums      HL1..HL5.  k_liq_sums's shape on three panels: (slice of MS_THREADS lanes, one
-//                     asset per lane) x (chunk of consecutive months).  The lead-in walks the
-//                     max_gap rows before the chunk for each asset's latest ranged row; then trips
-//                     of TRIP day rows of H, L and C, the next trip's loads in flight, a month's
-//                     values flushed as the walk passes its end.  No barrier, no LDS, no atomics,
-//                     no state in memory (csm_tune "rsums_chunks").  The first kernel here with
+//   k_range_sums      HL1..HL5.  The month walk of daytrip.h on three panels, one asset per lane:
+//                     the lead-in walks the max_gap rows before the chunk for each asset's latest
+//                     ranged row; then trips of TRIP day rows of H, L and C (csm_tune
+//                     "rsums_chunks").  The first kernel here with
 //                     log / exp: OCML's bodies are inlined, five logs (three without the overnight
 //                     shift), one exp, three square roots and three divisions a pair, so the walk
 //                     is bound by fp64 arithmetic, not by HBM; CS / AR are template flags, so a
@@ -38,7 +36,7 @@
 #define RGM_THREADS 64
 #define RGM_MAXW 12
 
-// "rsums_chunks":  month chunks of k_range_sums, 0 auto (rg_auto_chunks) | n >= 1 that many
+// "rsums_chunks":  month chunks of k_range_sums, 0 auto (scan.h auto_chunks) | n >= 1 that many
 // "rmodel_chunks": month chunks of k_range_model, 0 auto, one month per chunk | n >= 1 that many
 // (both clamped to T_m).  Every value gives the same bits.
 static int g_tune_rsums_chunks = 0;
@@ -180,20 +178,40 @@ __device__ __forceinline__ void rg_flush(const RgAcc& s, int64_t o, const RgOut&
   if (AR) out.SAR[o] = s.sar;
 }
 
-// Rows [d, d + TRIP) of the lane's asset from one panel; rows from dB on are NaN: days that are
-// not ranged, which change nothing.
-template <int TRIP>
-__device__ __forceinline__ void rg_load(double (&x)[TRIP], const double* __restrict__ X, int64_t N,
-                                        int64_t a, int64_t d, int64_t dB) {
-  const double* p = X + d * N + a;
-  if (d + TRIP <= dB) {   // (uniform) a whole trip: no predicate on any load
-#pragma unroll
-    for (int i = 0; i < TRIP; ++i) x[i] = p[(int64_t)i * N];
-  } else {
-#pragma unroll
-    for (int i = 0; i < TRIP; ++i) x[i] = d + i < dB ? p[(int64_t)i * N] : qnan();
+// k_range_sums's walker (daytrip.h): the lead-in on three panels, then H's, L's and C's rows; rows
+// past the chunk are NaN: days that are not ranged, which change nothing.
+template <int TRIP, bool CS, bool AR>
+struct RgWalker {
+  const double* __restrict__ H;
+  const double* __restrict__ L;
+  const double* __restrict__ C;
+  int64_t N, a;
+  int max_gap;
+  RgOut out;
+  RgLane lane;
+  RgAcc acc;
+  struct Rows {
+    double h[TRIP][1], l[TRIP][1], c[TRIP][1];
+  };
+
+  __device__ __forceinline__ void begin(int64_t dA) {
+    rg_lead_in<AR>(lane, H, L, C, N, a, dA, max_gap);
+    rg_reset(acc);
   }
-}
+  __device__ __forceinline__ void load(Rows& r, int64_t d, int64_t dB) const {
+    trip_load<TRIP, 1>(r.h, H, N, a, d, dB, qnan());
+    trip_load<TRIP, 1>(r.l, L, N, a, d, dB, qnan());
+    trip_load<TRIP, 1>(r.c, C, N, a, d, dB, qnan());
+  }
+  __device__ __forceinline__ void own(Rows&, int64_t, int64_t) const {}
+  __device__ __forceinline__ void step(const Rows& r, int i) {
+    rg_step<CS, AR>(acc, lane, r.h[i][0], r.l[i][0], r.c[i][0], max_gap);
+  }
+  __device__ __forceinline__ void flush(int m) {   // the pair state runs on
+    rg_flush<CS, AR>(acc, (int64_t)m * N + a, out);
+    rg_reset(acc);
+  }
+};
 
 template <int TRIP, bool CS, bool AR>
 __global__ __launch_bounds__(MS_THREADS) void k_range_sums(
@@ -202,58 +220,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_range_sums(
     RgOut out) {
   const int64_t a = (int64_t)blockIdx.x * MS_THREADS + threadIdx.x;
   if (a >= N) return;   // (no barrier anywhere below)
-  int m0, m1;
-  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
-  // the chunk's day rows and month ends, clipped as k_liq_sums clips them
-  const int64_t dA = ms_clip(ms[m0], 0, T_d), dB = ms_clip(ms[m1], dA, T_d);
-  int m = m0;
-  int64_t nb = ms_clip(ms[m0 + 1], dA, dB);   // end of month m
-  RgLane lane;
-  rg_lead_in<AR>(lane, H, L, C, N, a, dA, max_gap);
-  RgAcc acc;
-  rg_reset(acc);
-  auto next_month = [&]() {   // (uniform) month m is complete; the pair state runs on
-    rg_flush<CS, AR>(acc, (int64_t)m * N + a, out);
-    rg_reset(acc);
-    ++m;
-    nb = m < m1 ? ms_clip(ms[m + 1], dA, dB) : dB;
-  };
-  double hc[TRIP], hn[TRIP], lc[TRIP], ln[TRIP], cc[TRIP], cn[TRIP];
-  rg_load<TRIP>(hc, H, N, a, dA, dB);
-  rg_load<TRIP>(lc, L, N, a, dA, dB);
-  rg_load<TRIP>(cc, C, N, a, dA, dB);
-  for (int64_t d = dA; d < dB; d += TRIP) {
-    rg_load<TRIP>(hn, H, N, a, d + TRIP, dB);
-    rg_load<TRIP>(ln, L, N, a, d + TRIP, dB);
-    rg_load<TRIP>(cn, C, N, a, d + TRIP, dB);
-    if (d + TRIP <= nb) {   // (uniform) the trip lies inside month m: one straight block
-#pragma unroll
-      for (int i = 0; i < TRIP; ++i) rg_step<CS, AR>(acc, lane, hc[i], lc[i], cc[i], max_gap);
-    } else {
-#pragma unroll
-      for (int i = 0; i < TRIP; ++i) {
-        while (m < m1 && d + i >= nb) next_month();   // (zero-length months: several)
-        rg_step<CS, AR>(acc, lane, hc[i], lc[i], cc[i], max_gap);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < TRIP; ++i) {
-      hc[i] = hn[i];
-      lc[i] = ln[i];
-      cc[i] = cn[i];
-    }
-  }
-  while (m < m1) next_month();   // the last month, and whatever zero-length months follow it
-}
-
-// Auto chunk count: lq_auto_chunks's rule (liquidity.hip), about 32 (slice, chunk) workgroups per
-// CU and no chunk shorter than three months.
-static inline int rg_auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m) {
-  const int64_t want = (int64_t)32 * (ctx->n_cu > 0 ? ctx->n_cu : 256);
-  int64_t G = (want + slices - 1) / slices;
-  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
-  if (G > most) G = most;
-  return (int)G;
+  RgWalker<TRIP, CS, AR> w{H, L, C, N, a, max_gap, out};
+  month_walk<TRIP>(w, ms, T_m, G, T_d);
 }
 
 // ------------------------------------------------------------------------------- HL6
@@ -338,12 +306,9 @@ int csm_range_sums(csm_ctx* ctx, const double* H, const double* L, const double*
   if (max_gap < 1 || max_gap > DM_MAXGAP)
     return set_err(ctx, CSM_E_INVAL, "csm_range_sums: max_gap=%d is outside [1, %d]", max_gap,
                    DM_MAXGAP);
-  const int64_t slices = (N + MS_THREADS - 1) / MS_THREADS;
-  int64_t G = g_tune_rsums_chunks > 0 ? g_tune_rsums_chunks : rg_auto_chunks(ctx, slices, T_m);
-  if (G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
-  const int g = (int)G;
-  const dim3 grid((unsigned)slices, (unsigned)g);
+  // Auto chunk count: k_liq_sums's, about 32 workgroups per CU (scan.h auto_chunks)
+  const dim3 grid = month_grid(ctx, N, MS_THREADS, g_tune_rsums_chunks, 32, T_m);
+  const int g = (int)grid.y;
   const RgOut out{NRG, NPR, NCS, SPK, SCS, SAR};
   auto launch = [&](auto kernel) {
     hipLaunchKernelGGL(kernel, grid, dim3(MS_THREADS), 0, ctx->stream, H, L, C, T_d, N,

@@ -256,6 +256,28 @@ __device__ __forceinline__ void chunk_range(int T_m, int G, int g, int& m0, int&
   m1 = m0 + base + (g < rem ? 1 : 0);
 }
 
+// Auto chunk count of a kernel over (slice of assets) x (chunk of consecutive months) whose chunks
+// pay for their start (a lead-in, a window's warm-up): about per_cu (slice, chunk) workgroups per
+// CU, and no chunk shorter than three months.  per_cu is measured per kernel, at its caller.
+static inline int auto_chunks(const csm_ctx* ctx, int64_t slices, int T_m, int per_cu) {
+  const int64_t want = (int64_t)per_cu * (ctx->n_cu > 0 ? ctx->n_cu : 256);
+  int64_t G = (want + slices - 1) / slices;
+  const int64_t most = T_m / 3 > 0 ? T_m / 3 : 1;
+  if (G > most) G = most;
+  return (int)G;
+}
+
+// That kernel's grid: slices of per_slice assets x G chunks, G the tune value when it is >= 1,
+// else auto_chunks at per_cu, clamped to T_m and to what grid.y takes.
+static inline dim3 month_grid(const csm_ctx* ctx, int64_t N, int per_slice, int tune, int per_cu,
+                              int T_m) {
+  const int64_t slices = (N + per_slice - 1) / per_slice;
+  int64_t G = tune > 0 ? tune : auto_chunks(ctx, slices, T_m, per_cu);
+  if (G > T_m) G = T_m;
+  if (G > 65535) G = 65535;   // (grid.y)
+  return dim3((unsigned)slices, (unsigned)G);
+}
+
 // =====================================================================================
 // The month step's sites with an LDS ring (shared by k_momentum and k_signal): scan_step_on
 // with the LDS ring policy, and its form for two adjacent assets.

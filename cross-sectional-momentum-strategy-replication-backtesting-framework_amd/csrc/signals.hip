@@ -2,15 +2,9 @@
 // 52-week high and volatility-scaled momentum, with the realised volatility the cost model takes
 // as SIG.
 //
-//   k_month_stats     D1.  One pass over P.  The grid is (slice of assets) x (chunk of consecutive
-//                     months); a lane owns one asset (or two adjacent ones, 16-B loads and stores)
-//                     and walks the day rows of its chunk in trips of MS_TRIP rows, the next trip's
-//                     loads in flight while this one is reduced.  The months of a chunk are flushed
-//                     as the walk passes their ends; no month needs anything from another, so
-//                     there is no barrier, no LDS, no atomic and no state in memory, and the chunk
-//                     count only decides how many workgroups the launch has (csm_tune
-//                     "stats_chunks"): every count gives the same bits.  Per priced cell: one
-//                     division that depends on loaded values only, and one add on the SSW chain.
+//   k_month_stats     D1.  One pass over P: the month walk of daytrip.h, one or two assets per lane,
+//                     no lead-in (csm_tune "stats_chunks").  Per priced cell: one division that
+//                     depends on loaded values only, and one add on the SSW chain.
 //   k_window_signals  D2..D6.  A lane per asset walks the months: the stitch (the month's first
 //                     return, added last), the Jh / Jv windows on slot-major per-lane LDS rings
 //                     (the column layout of scan.h's ScanLane ring), each window summed again
@@ -66,27 +60,55 @@ __device__ __forceinline__ void ms_step(MsAcc& s, double x) {
   s.last = ok ? x : s.last;
 }
 
+// k_month_stats's walker (daytrip.h): one panel, no lead-in; rows past the chunk are ABSENT.
 template <int VEC>
-__device__ __forceinline__ void ms_flush(const MsAcc (&s)[VEC], int64_t o, double* __restrict__ PM,
-                                         double* __restrict__ P1, double* __restrict__ HI,
-                                         double* __restrict__ SSW, int32_t* __restrict__ NDW) {
-  double pm[VEC];
+struct MsWalker {
+  const double* __restrict__ P;
+  int64_t N, a;
+  double* __restrict__ PM;
+  double* __restrict__ P1;
+  double* __restrict__ HI;
+  double* __restrict__ SSW;
+  int32_t* __restrict__ NDW;
+  MsAcc acc[VEC];
+  struct Rows {
+    double x[MS_TRIP][VEC];
+  };
+
+  __device__ __forceinline__ void reset() {
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) pm[k] = s[k].anyp ? s[k].last : absent_val();
-  if (VEC == 2) {
-    if (PM) store_pair(PM + o, pm[0], pm[VEC - 1]);
-    store_pair(P1 + o, s[0].p1, s[VEC - 1].p1);
-    store_pair(HI + o, s[0].hi, s[VEC - 1].hi);
-    store_pair(SSW + o, s[0].ss, s[VEC - 1].ss);
-    *reinterpret_cast<int2*>(NDW + o) = make_int2(s[0].nd, s[VEC - 1].nd);
-  } else {
-    if (PM) PM[o] = pm[0];
-    P1[o] = s[0].p1;
-    HI[o] = s[0].hi;
-    SSW[o] = s[0].ss;
-    NDW[o] = s[0].nd;
+    for (int k = 0; k < VEC; ++k) ms_reset(acc[k]);
   }
-}
+  __device__ __forceinline__ void begin(int64_t) { reset(); }
+  __device__ __forceinline__ void load(Rows& r, int64_t d, int64_t dB) const {
+    trip_load<MS_TRIP, VEC>(r.x, P, N, a, d, dB, absent_val());
+  }
+  __device__ __forceinline__ void own(Rows&, int64_t, int64_t) const {}
+  __device__ __forceinline__ void step(const Rows& r, int i) {
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) ms_step(acc[k], r.x[i][k]);
+  }
+  __device__ __forceinline__ void flush(int m) {
+    const int64_t o = (int64_t)m * N + a;
+    double pm[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) pm[k] = acc[k].anyp ? acc[k].last : absent_val();
+    if (VEC == 2) {
+      if (PM) store_pair(PM + o, pm[0], pm[VEC - 1]);
+      store_pair(P1 + o, acc[0].p1, acc[VEC - 1].p1);
+      store_pair(HI + o, acc[0].hi, acc[VEC - 1].hi);
+      store_pair(SSW + o, acc[0].ss, acc[VEC - 1].ss);
+      *reinterpret_cast<int2*>(NDW + o) = make_int2(acc[0].nd, acc[VEC - 1].nd);
+    } else {
+      if (PM) PM[o] = pm[0];
+      P1[o] = acc[0].p1;
+      HI[o] = acc[0].hi;
+      SSW[o] = acc[0].ss;
+      NDW[o] = acc[0].nd;
+    }
+    reset();
+  }
+};
 
 template <int VEC>
 __global__ __launch_bounds__(MS_THREADS) void k_month_stats(
@@ -95,48 +117,8 @@ __global__ __launch_bounds__(MS_THREADS) void k_month_stats(
     double* __restrict__ SSW, int32_t* __restrict__ NDW) {
   const int64_t a = ((int64_t)blockIdx.x * MS_THREADS + threadIdx.x) * VEC;
   if (a >= N) return;   // (no barrier anywhere below)
-  int m0, m1;
-  chunk_range(T_m, G, (int)blockIdx.y, m0, m1);   // G <= T_m: at least one month
-  // the chunk's day rows, clipped to the panel; every month end is clipped to them in turn, so no
-  // calendar makes the walk read outside [dA, dB) or store outside months [m0, m1)
-  const int64_t dA = ms_clip(ms[m0], 0, T_d), dB = ms_clip(ms[m1], dA, T_d);
-  int m = m0;
-  int64_t nb = ms_clip(ms[m0 + 1], dA, dB);   // end of month m
-  MsAcc acc[VEC];
-#pragma unroll
-  for (int k = 0; k < VEC; ++k) ms_reset(acc[k]);
-  auto next_month = [&]() {   // (uniform) month m is complete
-    ms_flush<VEC>(acc, (int64_t)m * N + a, PM, P1, HI, SSW, NDW);
-#pragma unroll
-    for (int k = 0; k < VEC; ++k) ms_reset(acc[k]);
-    ++m;
-    nb = m < m1 ? ms_clip(ms[m + 1], dA, dB) : dB;
-  };
-  double cur[MS_TRIP][VEC], nxt[MS_TRIP][VEC];
-  ms_load<VEC>(cur, P, N, a, dA, dB);
-  for (int64_t d = dA; d < dB; d += MS_TRIP) {
-    ms_load<VEC>(nxt, P, N, a, d + MS_TRIP, dB);
-    if (d + MS_TRIP <= nb) {   // (uniform) the trip lies inside month m: one straight block
-#pragma unroll
-      for (int i = 0; i < MS_TRIP; ++i) {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) ms_step(acc[k], cur[i][k]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < MS_TRIP; ++i) {
-        while (m < m1 && d + i >= nb) next_month();   // (zero-length months: several)
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) ms_step(acc[k], cur[i][k]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MS_TRIP; ++i) {
-#pragma unroll
-      for (int k = 0; k < VEC; ++k) cur[i][k] = nxt[i][k];
-    }
-  }
-  while (m < m1) next_month();   // the last month, and whatever zero-length months follow it
+  MsWalker<VEC> w{P, N, a, PM, P1, HI, SSW, NDW};
+  month_walk<MS_TRIP>(w, ms, T_m, G, T_d);
 }
 
 // ---------------------------------------------------------------------------- D2..D6
@@ -292,13 +274,10 @@ int csm_month_stats(csm_ctx* ctx, const double* P, int64_t T_d, int64_t N,
   const bool v2 = (N % 2 == 0) && aligned16(P) && (!PM || aligned16(PM)) && aligned16(P1) &&
                   aligned16(HI) && aligned16(SSW) && aligned8(NDW);
   const int vec = v2 ? 2 : 1;
-  const int64_t slices = (N + (int64_t)MS_THREADS * vec - 1) / ((int64_t)MS_THREADS * vec);
   // month chunks: T_m x slices workgroups fill the chip whatever the panel's width
-  int64_t G = g_tune_stats_chunks;
-  if (G < 1 || G > T_m) G = T_m;
-  if (G > 65535) G = 65535;   // (grid.y)
-  const int g = (int)G;
-  const dim3 grid((unsigned)slices, (unsigned)g);
+  const dim3 grid = month_grid(ctx, N, MS_THREADS * vec,
+                               g_tune_stats_chunks > 0 ? g_tune_stats_chunks : T_m, 0, T_m);
+  const int g = (int)grid.y;
   if (v2)
     hipLaunchKernelGGL(k_month_stats<2>, grid, dim3(MS_THREADS), 0, ctx->stream, P, T_d, N,
                        month_start, T_m, g, PM, P1, HI, SSW, NDW);
