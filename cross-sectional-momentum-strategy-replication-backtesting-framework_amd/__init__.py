@@ -39,12 +39,15 @@ a Python identifier).  Public API (reference file:line it replaces):
                                         volume panels (rules Q1..Q6)
   Engine.range_sums / range_model       Parkinson volatility, Corwin-Schultz and Abdi-Ranaldo bid-ask
   range_signals                         spreads from the daily high, low and close (rules HL1..HL6)
+  Engine.asym_sums / asym_model         information discreteness, signed jump variation, downside
+  asymmetry_signals / frog_in_the_pan   semi-volatility and downside beta from the daily returns; momentum
+                                        inside information-discreteness bins (rules AS1..AS7)
   SweepRunner                           (J, K) grids over panels / bootstrap panels (C3, C5)
   Engine.turnover_features              src/features.py:60-107 on the device (bit-exact)
   momentum_volume_double_sort           LeSw00 10 x 3 momentum x turnover sort
 """
 from ._lib import ABSENT_BITS, CsmError, CsmUnavailable, lib_path, load_library
-from .engine import (DailyFModelOut, DailyFSums, DailyModelOut, DailyOut, DailySums, Engine, FactorModelOut, FamaMacBethOut, GroupStatsOut, ICDecayOut, LiqModelOut, LiqSums,
+from .engine import (AsymModelOut, AsymSums, DailyFModelOut, DailyFSums, DailyModelOut, DailyOut, DailySums, Engine, FactorModelOut, FamaMacBethOut, GroupStatsOut, ICDecayOut, LiqModelOut, LiqSums,
                      MarketModelOut,
                      MonthStats, NeweyWestOut, PipelineOut, PortfolioOut, RangeModelOut, RangeSums,
                      RankICOut, SignalsOut,
@@ -60,6 +63,7 @@ from .regress import FamaMacBethResult, fama_macbeth
 from .ic import ICResult, information_coefficient
 from .liquidity import LIQUIDITY_COLUMNS, liquidity_signals
 from .ranges import RANGE_COLUMNS, range_signals
+from .asym import ASYMMETRY_COLUMNS, FipResult, asymmetry_signals, frog_in_the_pan
 from .panel import DensePanel, from_long, month_offsets, monthly_frame, range_from_long
 from .replication import (ReplicationResult, assign_deciles_per_date, daily_portfolio_returns,
                           monthly_replication)
@@ -83,4 +87,6 @@ __all__ = [
     "FactorModelOut", "DailyFSums", "DailyFModelOut", "ResidualMomentumResult", "align_factors",
     "residual_momentum", "LiqSums", "LiqModelOut", "LIQUIDITY_COLUMNS", "liquidity_signals",
     "RangeSums", "RangeModelOut", "RANGE_COLUMNS", "range_signals", "range_from_long",
+    "AsymSums", "AsymModelOut", "ASYMMETRY_COLUMNS", "FipResult", "asymmetry_signals",
+    "frog_in_the_pan",
 ]

@@ -119,6 +119,10 @@ SIGNATURES = {
                                       _p, _p, _p]),
     "csm_range_model": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _i32, _i64, _i32, _i32, _f64,
                                        _p, _p, _p, _p]),
+    "csm_asym_sums": (ctypes.c_int, [_p, _p, _p, _i64, _i64, _p, _i32, _i32, _i32, _i32, _p, _p, _p,
+                                     _p, _p, _p, _p, _p, _p, _p]),
+    "csm_asym_model": (ctypes.c_int, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i64,
+                                      _i32, _i32, _i32, _i32, _p, _p, _p, _p, _p, _p]),
     "csm_xs_regress": (ctypes.c_int, [_p, _p, _p, _i32, _p, _i32, _i64, _i32, _f64, _i32, _p, _p,
                                       _p]),
     "csm_newey_west": (ctypes.c_int, [_p, _p, _i32, _i32, _i64, _i32, _p, _p, _p, _p]),

@@ -21,7 +21,7 @@ int csm_abi_version(void) { return CSM_ABI_VERSION; }
 int csm_tune(const char* key, int value) {
   for (auto stage : {csm_tune_scans, csm_tune_signal, csm_tune_signal_tc, csm_tune_deciles,
                      csm_tune_shards, csm_tune_signals, csm_tune_market, csm_tune_groups,
-                     csm_tune_dailymkt, csm_tune_liq, csm_tune_range})
+                     csm_tune_dailymkt, csm_tune_liq, csm_tune_range, csm_tune_asym})
     if (stage(key, value) == CSM_OK) return CSM_OK;
   return csm_tune_portfolio(key, value);
 }

@@ -176,6 +176,7 @@ int csm_tune_groups(const char* key, int value);      // groups.hip
 int csm_tune_dailymkt(const char* key, int value);    // dailymkt.hip
 int csm_tune_liq(const char* key, int value);         // liquidity.hip
 int csm_tune_range(const char* key, int value);       // range.hip
+int csm_tune_asym(const char* key, int value);        // asym.hip
 }
 // The fused month-end + scan launch behind every csm_signal* entry point and csm_pipeline
 // (signal.hip): k_signal_tail or k_signal for the panel's width and alignment and the signal

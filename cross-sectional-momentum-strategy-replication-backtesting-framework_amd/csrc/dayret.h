@@ -1,6 +1,7 @@
 // dayret.h -- rule V1's daily return with a gap bound, as the kernels that walk day rows with an
 // asset's last priced price in registers take it: k_daily_market, k_daily_sums and k_daily_fsums
-// (dailymkt.hip, rules V2, V3, MF6) and k_liq_sums (liquidity.hip, rule Q2).
+// (dailymkt.hip, rules V2, V3, MF6), k_liq_sums (liquidity.hip, rule Q2) and k_asym_sums (asym.hip,
+// rule AS2).
 #pragma once
 #include "csm_common.h"
 

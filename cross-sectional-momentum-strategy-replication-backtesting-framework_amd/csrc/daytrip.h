@@ -1,6 +1,7 @@
 // daytrip.h -- the month walk of the kernels that sum the daily panels by (month, asset):
 // k_month_stats (signals.hip, rule D1), k_daily_sums and k_daily_fsums (dailymkt.hip, rules V3 and
-// MF6), k_liq_sums (liquidity.hip, rule Q2) and k_range_sums (range.hip, rules HL1..HL5).
+// MF6), k_liq_sums (liquidity.hip, rule Q2), k_range_sums (range.hip, rules HL1..HL5) and
+// k_asym_sums (asym.hip, rule AS2).
 //
 // The grid is (slice of MS_THREADS lanes) x (chunk of consecutive months, scan.h chunk_range); a
 // lane owns one asset, or two adjacent ones (16-B loads and stores), and walks the day rows of its

@@ -238,6 +238,33 @@ class RangeModelOut:
     NOBS: torch.Tensor | None = None     # int32, pairs in the window
 
 
+class AsymSums(NamedTuple):
+    """csm_asym_sums (rule AS2), each [T_m][N]: a month's return days by the sign of the return,
+    their squared returns, and the market-model sums over the days on one side of FD; asym_model's
+    input.  The five side panels are None when no FD was given."""
+    ND: torch.Tensor                     # int32, days with a return (rule V1)
+    NUP: torch.Tensor                    # int32, days with r > 0
+    NDN: torch.Tensor                    # int32, days with r < 0
+    SUP: torch.Tensor                    # sum of r * r over the days with r > 0
+    SDN: torch.Tensor                    # sum of r * r over the days with r < 0
+    NB: torch.Tensor | None = None       # int32, return days with f on the side
+    BR: torch.Tensor | None = None       # sum of r over them
+    BF: torch.Tensor | None = None       # sum of f
+    BFF: torch.Tensor | None = None      # sum of f * f
+    BRF: torch.Tensor | None = None      # sum of r * f
+
+
+@dataclass
+class AsymModelOut:
+    """csm_asym_model (rule AS3), each [T_m][N]; None = not asked for."""
+    ID: torch.Tensor | None = None       # information discreteness (Da, Gurun and Warachka 2014)
+    RSJ: torch.Tensor | None = None      # signed jump variation over the realised variance
+    DSVOL: torch.Tensor | None = None    # downside semi-volatility, daily
+    DNBETA: torch.Tensor | None = None   # slope of the daily returns on f over the side days
+    NOBS: torch.Tensor | None = None     # int32, return days in the window
+    NSIDE: torch.Tensor | None = None    # int32, side days in the window
+
+
 @dataclass
 class XsRegressOut:
     """csm_xs_regress (rules R1..R5): one cross-sectional regression per month."""
@@ -1324,6 +1351,69 @@ class Engine:
                    4.0 * math.log(2.0), *(_ptr(o.get(k)) for k in self.RANGE_OUTPUTS))
         return RangeModelOut(**o)
 
+    def asym_sums(self, P, month_start, FD=None, side=-1, max_gap=10,
+                  max_month_days=None) -> AsymSums:
+        """csm_asym_sums (rules AS1, AS2): one pass over the daily prices P for each (month,
+        asset)'s return days by the sign of the return and their squared returns and, with a
+        daily series FD [T_d] (daily_market's, or any other), the market-model sums over the days
+        with FD < 0 (side -1) or FD > 0 (side +1)."""
+        T_d, N = P.shape
+        T_m = month_start.numel() - 1
+        _need(P, "P", torch.float64, (T_d, N), self.device)
+        _need(month_start, "month_start", torch.int64, (T_m + 1,), self.device)
+        if FD is not None:
+            _need(FD, "FD", torch.float64, (T_d,), self.device)
+        if max_month_days is None:
+            max_month_days, _ = self.month_days(month_start)
+        ND, NUP, NDN = (self.empty((T_m, N), torch.int32) for _ in range(3))
+        SUP, SDN = self.empty((T_m, N)), self.empty((T_m, N))
+        NB = BR = BF = BFF = BRF = None
+        if FD is not None:
+            NB = self.empty((T_m, N), torch.int32)
+            BR, BF, BFF, BRF = (self.empty((T_m, N)) for _ in range(4))
+        self._call("csm_asym_sums", _ptr(P), _ptr(FD), T_d, N, _ptr(month_start), T_m,
+                   int(max_month_days), int(max_gap), int(side), _ptr(ND), _ptr(NUP), _ptr(NDN),
+                   _ptr(SUP), _ptr(SDN), _ptr(NB), _ptr(BR), _ptr(BF), _ptr(BFF), _ptr(BRF))
+        return AsymSums(ND, NUP, NDN, SUP, SDN, NB, BR, BF, BFF, BRF)
+
+    ASYM_OUTPUTS = ("ID", "RSJ", "DSVOL", "DNBETA", "NOBS", "NSIDE")
+
+    def asym_model(self, sums: AsymSums, window=12, skip=0, M=None, min_obs=None, min_side=None,
+                   outputs=None) -> AsymModelOut:
+        """csm_asym_model (rule AS3) on asym_sums' panels over the `window` calendar months
+        (1..36) that end `skip` months back (0..12): the information discreteness ID, signed by
+        the formation return M [T_m][N] (mom_J with J = window and the same skip), the signed
+        jump variation RSJ, the downside semi-volatility DSVOL, the side beta DNBETA, NOBS and
+        NSIDE.  min_obs counts return days (default 15 * window), min_side side days (default
+        max(2, 5 * window)).  outputs: the AsymModelOut fields to compute (default: all the sums
+        and M given allow)."""
+        T_m, N = sums.SUP.shape
+        for k in ("ND", "NUP", "NDN", "NB"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.int32, (T_m, N), self.device)
+        for k in ("SUP", "SDN", "BR", "BF", "BFF", "BRF"):
+            t = getattr(sums, k)
+            if t is not None:
+                _need(t, k, torch.float64, (T_m, N), self.device)
+        if M is not None:
+            _need(M, "M", torch.float64, (T_m, N), self.device)
+        if outputs is None:
+            outputs = tuple(k for k in self.ASYM_OUTPUTS
+                            if not (k == "ID" and M is None)
+                            and not (k in ("DNBETA", "NSIDE") and sums.NB is None))
+        unknown = set(outputs) - set(self.ASYM_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        window = int(window)
+        min_obs = 15 * window if min_obs is None else int(min_obs)
+        min_side = max(2, 5 * window) if min_side is None else int(min_side)
+        o = {k: self.empty((T_m, N), torch.int32 if k in ("NOBS", "NSIDE") else torch.float64)
+             for k in outputs}
+        self._call("csm_asym_model", *(_ptr(t) for t in sums), _ptr(M), T_m, N, window, int(skip),
+                   min_obs, min_side, *(_ptr(o.get(k)) for k in self.ASYM_OUTPUTS))
+        return AsymModelOut(**o)
+
     @staticmethod
     def lagged(F, lags):
         """[T][1 + lags]: column k is the series F [T] shifted down k rows, NaN in its first k
@@ -1983,8 +2073,9 @@ class Engine:
     DAILY_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL", "dskew": "DSKEW", "max": "DMAX"}
     LIQ_SIGNALS = {"illiq": "ILLIQ", "dvol": "DVOL", "zret": "ZRET"}
     RANGE_SIGNALS = {"pkvol": "PKVOL", "cs_spread": "CSSPR", "ar_spread": "ARSPR"}
-    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS, *RANGE_SIGNALS,
-                   *LIQ_SIGNALS)
+    ASYM_SIGNALS = {"info_disc": "ID", "rsj": "RSJ", "dsvol": "DSVOL", "dnbeta": "DNBETA"}
+    RUN_SIGNALS = ("high52", "mom_vol", *MARKET_SIGNALS, *DAILY_SIGNALS, *ASYM_SIGNALS,
+                   *RANGE_SIGNALS, *LIQ_SIGNALS)
 
     def daily_signals(self, P, month_start, names, window=None, min_obs=None, max_gap=10):
         """{name: [T_m][N]} for names of DAILY_SIGNALS (rules V1..V4): the daily market, one pass
@@ -2026,6 +2117,39 @@ class Engine:
                               outputs=tuple(self.RANGE_SIGNALS[n] for n in names))
         return {n: getattr(rm, self.RANGE_SIGNALS[n]) for n in names}
 
+    def asym_signals(self, P, month_start, names, J=12, skip=1, window=None, min_obs=None,
+                     max_gap=10, PM=None):
+        """{name: [T_m][N]} for names of ASYM_SIGNALS (rules AS1..AS3): one pass over P for the
+        month sums and one model call per window.  "info_disc" always covers the J months that
+        end `skip` months back, signed by momentum(PM, J, skip)'s mom_J (PM None: month_end's);
+        `window` does not apply to it.  window None: 1 month for "rsj" and "dsvol", 12 for
+        "dnbeta", whose factor is daily_market(P, max_gap)'s series and whose side is -1; these
+        three end at the month itself.  min_obs counts return days (default 15 * window); for
+        "dnbeta" it counts the down-market return days (default max(2, 5 * window), and at least
+        2 when given)."""
+        FD = self.daily_market(P, max_gap)[0] if "dnbeta" in names else None
+        sums = self.asym_sums(P, month_start, FD, -1, max_gap)
+        calls = {}
+        for n in names:
+            if n == "info_disc":
+                key = (int(J), int(skip))
+            else:
+                key = ((12 if n == "dnbeta" else 1) if window is None else int(window), 0)
+            calls.setdefault(key, []).append(n)
+        out = {}
+        for (w, s), group in calls.items():
+            M = None
+            if "info_disc" in group:
+                if PM is None:
+                    PM, _ = self.month_end(P, month_start)
+                _, M, _ = self.momentum(PM, J, skip)
+            am = self.asym_model(sums, w, s, M, min_obs,
+                                 None if min_obs is None else max(2, int(min_obs)),
+                                 outputs=tuple(self.ASYM_SIGNALS[n] for n in group))
+            for n in group:
+                out[n] = getattr(am, self.ASYM_SIGNALS[n])
+        return out
+
     DAILY_FACTOR_SIGNALS = {"dbeta": "DBETA", "divol": "DIVOL"}   # the daily signals factors= serves
 
     def run_signal(self, P, month_start, signal, J=12, skip=1, n_bins=10, window=12,
@@ -2054,9 +2178,17 @@ class Engine:
         [T_d][N] (rules HL1..HL6): "pkvol", "cs_spread" or "ar_spread".  For these a `window`
         left at its default means 1 month, min_obs counts days (default 15 * window), and NR is
         the next return of P's month-end prices.  These three need HLC; HLC with V or factors
+        raises.
+        Or on an asymmetry signal of the daily returns (rules AS1..AS7): "info_disc", the
+        information discreteness of the J months that end `skip` months back, signed by mom_J
+        (`window` does not apply), "rsj" or "dsvol" (a `window` left at its default means 1
+        month), or "dnbeta", the beta on the down days of the equal-weight daily market (12
+        months).  min_obs counts days as in asym_signals.  factors, V or HLC with one of these
         raises."""
         if signal not in self.RUN_SIGNALS:
             raise ValueError(f"signal must be one of {self.RUN_SIGNALS}, got {signal!r}")
+        if signal in self.ASYM_SIGNALS and not (factors is None and V is None and HLC is None):
+            raise ValueError(f"signal {signal!r} takes no factors, V or HLC")
         if signal in self.LIQ_SIGNALS and V is None:
             raise ValueError(f"signal {signal!r} needs the daily volume panel V")
         if V is not None and factors is not None:
@@ -2088,6 +2220,10 @@ class Engine:
         elif signal in self.DAILY_SIGNALS:
             S = self.daily_signals(P, month_start, (signal,), None if window == 12 else window,
                                    min_obs)[signal]
+            NR = self.next_ret(st.PM, S)
+        elif signal in self.ASYM_SIGNALS:
+            S = self.asym_signals(P, month_start, (signal,), J, skip,
+                                  None if window == 12 else window, min_obs, PM=st.PM)[signal]
             NR = self.next_ret(st.PM, S)
         elif signal in self.LIQ_SIGNALS:
             S = self.liq_signals(P, V, month_start, (signal,), window, min_obs)[signal]

@@ -35,7 +35,9 @@ def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None,
     the monthly market model's, 1 for "divol", "dskew" and "max", 12 for the liquidity names
     "illiq", "dvol" and "zret", which need the daily volume panel V [T_d][N], and 1 for the range
     names "pkvol", "cs_spread" and "ar_spread", which need the daily high, low and close panels
-    HLC = (H, L, C)."""
+    HLC = (H, L, C).  The asymmetry names follow Engine.asym_signals: "info_disc" covers the J
+    months that end `skip` months back whatever `window` is, "rsj" and "dsvol" default to 1 month
+    and "dnbeta" to 12."""
     unknown = [n for n in names if n not in SIGNAL_NAMES]
     if unknown:
         raise ValueError(f"signals must be among {SIGNAL_NAMES}, got {unknown}")
@@ -70,6 +72,9 @@ def build_signals(eng: Engine, P, month_start, names, J=12, skip=1, window=None,
     dsig = [n for n in names if n in Engine.DAILY_SIGNALS]
     if dsig:
         out.update(eng.daily_signals(P, month_start, dsig, window))
+    asym = [n for n in names if n in Engine.ASYM_SIGNALS]
+    if asym:
+        out.update(eng.asym_signals(P, month_start, asym, J, skip, window, PM=st.PM))
     if liq:
         out.update(eng.liq_signals(P, V, month_start, liq, window))
     if rng:

@@ -91,7 +91,9 @@ int csm_abi_version(void);
  * n >= 1 that many, clamped to T_m), "lsums_pair" (csm_liq_sums: 0 one asset per lane | 1 two
  * where the panels allow; the same bits from all three), "rsums_chunks" / "rmodel_chunks"
  * (csm_range_sums's and csm_range_model's month chunks: 0 auto | n >= 1 that many, clamped to
- * T_m; the same bits).
+ * T_m; the same bits), "asums_chunks" / "amodel_chunks" (csm_asym_sums's and csm_asym_model's month
+ * chunks: 0 auto | n >= 1 that many, clamped to T_m), "asums_pair" (csm_asym_sums: 0 auto, one
+ * asset per lane | 1 one per lane | 2 two where the panels allow; the same bits from all).
  * Returns CSM_E_INVAL for an unknown key or value. */
 int csm_tune(const char* key, int value);
 /* Profiling aids: "dec_timing" = device int64 buffer [T_m][9] that k_deciles fills with
@@ -991,6 +993,66 @@ int csm_range_model(csm_ctx* ctx, const int32_t* NRG, const int32_t* NPR, const 
                     const double* SPK, const double* SCS, const double* SAR, int32_t T_m, int64_t N,
                     int32_t Wm, int32_t min_obs, double c4, double* PKVOL, double* CSSPR,
                     double* ARSPR, int32_t* NOBS);
+
+/*
+ * Asymmetry signals of the daily returns (rules AS1..AS7 in DESIGN.md section 7; no reference
+ * counterpart): the information discreteness of Da, Gurun and Warachka (2014), the signed jump
+ * variation RSJ and the downside semi-volatility (Barndorff-Nielsen, Kinnebrock and Shephard 2010;
+ * Bollerslev, Li and Zhao 2020), and the downside (or upside) beta (Bawa and Lindenberg 1977; Ang,
+ * Chen and Xing 2006).  fp64 without contraction, every sum sequential in day (then month) order
+ * from zero with one rounding per written operation, so two calls, and every launch shape, give the
+ * same bits.
+ *
+ * AS1: P [T_d][N]; r[d][a] is csm_daily_market's daily return (V1) with max_gap in [1, 32].
+ * FD [T_d] nullable in: f = FD[d], which may be NaN (csm_daily_market's MKTD, or any series).
+ * side is -1 or +1: day d is on the side iff f < 0 (side -1) or f > 0 (side +1).
+ *
+ * csm_asym_sums (AS2): per (month t, asset), over the days d of [month_start[t], month_start[t+1])
+ * in day order from zero, rr = r * r:
+ *   return day (r not NaN):                    ND += 1
+ *   r > 0:                                     NUP += 1, SUP += rr
+ *   r < 0:                                     NDN += 1, SDN += rr   (a zero return: ND only)
+ *   side day (r, f not NaN, f on the side):    NB += 1, BR += r, BF += f, BFF += f * f, BRF += r * f
+ *   ND, NUP, NDN [T_m][N] int32 out; SUP, SDN [T_m][N] out.  NB [T_m][N] int32 and BR, BF, BFF, BRF
+ *   [T_m][N] out are given if and only if FD is (CSM_E_INVAL otherwise).  A month without a day
+ *   gives zeros.
+ *   max_month_days in [1, 32], csm_month_stats's bound
+ * Any N >= 1, one asset per lane; under csm_tune "asums_pair" = 2 even N with a 16-B aligned P and
+ * f64 outputs and 8-B aligned int32 outputs takes two assets per lane (it measured slower, so it is
+ * not the default), the same bits.  "asums_chunks" (csm_tune: 0 auto | n >= 1 month chunks, clamped to T_m) only changes how
+ * many workgroups there are.  No row before month_start[0] - max_gap (clipped to 0) and none at or
+ * past month_start[T_m] is read.
+ *
+ * csm_asym_model (AS3) over the Wm calendar months j = t-skip-Wm+1 .. t-skip (t-skip-Wm+1 >= 0):
+ * each AS2 value added over j oldest first from zero into nd, nup, ndn, sup, sdn, nb, br, bf, bff,
+ * brf; counts enter the arithmetic as (double):
+ *   ID     = q if m > 0, -q if m < 0, 0.0 if m == 0, NaN if m is NaN, with q = (ndn - nup) / nd and
+ *            m = M[t][a], the caller's formation return (mom_J with J = Wm and the same skip):
+ *            defined iff nd >= min_obs
+ *   RSJ    = (sup - sdn) / (sup + sdn): defined iff nd >= min_obs and sup + sdn > 0
+ *   DSVOL  = sqrt(sdn / nd): defined iff nd >= min_obs
+ *   DNBETA = crf / cff, mf = bf / nb, cff = bff - bf * mf, crf = brf - br * mf (csm_daily_model's
+ *            form): defined iff nb >= min_side and cff > 0
+ *   NOBS   = nd, NSIDE = nb (int32; 0 before the first whole window)
+ *   1 <= Wm <= 36;  0 <= skip <= 12;  min_obs >= 1, min_side >= 2 (days);  T_m >= 1;  any N >= 1
+ *   M [T_m][N] nullable in; NB, BR, BF, BFF, BRF nullable in, together
+ *   ID, RSJ, DSVOL, DNBETA [T_m][N] out, NOBS, NSIDE [T_m][N] int32 out: NaN where not defined;
+ *       every one nullable, at least one given; ID needs M, DNBETA and NSIDE need the five side
+ *       panels
+ * "amodel_chunks" (csm_tune: 0 auto, one month per chunk | n >= 1 that many, clamped to T_m) only
+ * changes how many workgroups there are; only the panels a requested output depends on are read.
+ * The next return of any of these signals is csm_next_ret's (AS4).
+ */
+int csm_asym_sums(csm_ctx* ctx, const double* P, const double* FD, int64_t T_d, int64_t N,
+                  const int64_t* month_start, int32_t T_m, int32_t max_month_days, int32_t max_gap,
+                  int32_t side, int32_t* ND, int32_t* NUP, int32_t* NDN, double* SUP, double* SDN,
+                  int32_t* NB, double* BR, double* BF, double* BFF, double* BRF);
+int csm_asym_model(csm_ctx* ctx, const int32_t* ND, const int32_t* NUP, const int32_t* NDN,
+                   const double* SUP, const double* SDN, const int32_t* NB, const double* BR,
+                   const double* BF, const double* BFF, const double* BRF, const double* M,
+                   int32_t T_m, int64_t N, int32_t Wm, int32_t skip, int32_t min_obs,
+                   int32_t min_side, double* ID, double* RSJ, double* DSVOL, double* DNBETA,
+                   int32_t* NOBS, int32_t* NSIDE);
 
 /*
  * Fama-MacBeth (1973) cross-sectional regressions (rules R1..R6 in DESIGN.md section 7; the
